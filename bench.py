@@ -17,6 +17,14 @@ child `torch.distributed.run` started before anything touches the GPU.
 listed devices (psg_config.devices, one host thread per device — the JVM's route,
 psync/runtime/Runtime.scala:43-57), I instances per device. Timing: barrier +
 torch.cuda.synchronize() on both sides of exactly K steps, max over ranks.
+
+A plain run sets up, warms up, times the K steps and prints the headline line.
+`--full` adds what takes runs or files of its own: the other value domains
+(`--variants`), the roofline against the committed PMC profile and the CPU
+baseline. `--dump-outputs DIR` writes what the last timed step returned (the batch
+summary, and the decide results of a fixed seeded sample of instances) as
+DIR/<name>.npy; the inputs are a function of the arguments alone, so two builds
+can be compared array for array.
 """
 import argparse
 import json
@@ -50,14 +58,23 @@ def parse(argv=None):
     ap.add_argument("--n", type=int, default=64)
     ap.add_argument("--rounds", type=int, default=20)
     ap.add_argument("--V", type=int, default=64, help="value-domain size of the headline line")
-    ap.add_argument("--variants", default="2,4", help="other V values reported beside the headline")
+    ap.add_argument("--variants", default="2,4",
+                    help="other V values reported beside the headline (with --full; ignored without)")
     ap.add_argument("--seed", type=int, default=2)
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU-baseline sample length")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0,
+                    help="target CPU-baseline sample length (with --full; ignored without)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full without the CPU baseline (a plain run never takes it)")
     ap.add_argument("--device-list", default="",
                     help="one process, one psg context over these HIP devices (e.g. 0,1,2,3)")
     ap.add_argument("--dry-run", action="store_true",
                     help="set up the ranks (gloo) and print the plan without touching a GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the --variants series, the roofline against the committed PMC "
+                         "profile and the CPU baseline (a plain run times the headline only and, by choice, "
+                         "prints variants, cpu_baseline and roofline.achieved / peak / frac / traffic as null)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy")
     return ap.parse_args(argv)
 
 
@@ -224,9 +241,46 @@ def cpu_baseline(cfg, target_s):
     }
 
 
-def run_variant(rank, world, args, V, steps, warmup, devices=None):
+DUMP_SAMPLE = 65536  # instances whose decide results --dump-outputs keeps (2 x 16 MiB at n = 64)
+
+
+def _limbs16(v):
+    """A 64-bit counter as four 16-bit limbs (low first), each exact in a float64."""
+    v &= (1 << 64) - 1
+    return [(v >> (16 * k)) & 0xFFFF for k in range(4)]
+
+
+def dump_outputs(out_dir, gr, last, begin, count, seed):
+    """--dump-outputs: what the last timed gr.run(begin, count) gave its caller, as float arrays.
+    summary / fail_count / term_hist / digest are the returned psg_summary; decision and
+    decision_round are the batch's decide results (psg_copy_decisions) of a fixed, seeded
+    sample of its instances, whose global ids are sample_ids. psg_copy_decisions has no
+    partial form, so the whole batch crosses to the host first (2 x 2.56 GB at the default
+    1e7 x 64): about 0.2 s on top of a plain run's 3.1 s on one MI355X."""
+    import numpy as np
+    s = last.summary
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {
+        "summary": np.array([s.instances, s.process_rounds, s.active_process_rounds, s.live_instance_rounds,
+                             s.decided_processes], np.float64),
+        "fail_count": np.array(list(s.fail_count), np.float64),
+        "term_hist": np.array([s.term_hist[i] for i in range(last.rounds + 2)], np.float64),
+        "digest": np.array(_limbs16(int(s.digest)), np.float64),
+    }
+    dec, dr = gr._ctx.copy_decisions_np()  # [count][n] each, the last batch as it lies in HBM
+    rows = np.arange(count) if count <= DUMP_SAMPLE else \
+        np.sort(np.random.default_rng(seed).choice(count, DUMP_SAMPLE, replace=False))
+    arrays["sample_ids"] = (rows + begin).astype(np.float64)
+    arrays["decision"] = dec[rows].astype(np.float32)  # values lie in 1..V: exact
+    arrays["decision_round"] = dr[rows].astype(np.float32)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def run_variant(rank, world, args, V, steps, warmup, devices=None, dump_dir=""):
     """One timed series. Under ranks: this rank's shard on its LOCAL_RANK device. With a
-    device list: one context over `devices`, I instances per device."""
+    device list: one context over `devices`, I instances per device. dump_dir: rank 0 writes
+    its last step's outputs there (dump_outputs), after the clock has stopped."""
     dev = int(os.environ.get("LOCAL_RANK", 0))
     per = args.instances
     alg = psync.OTR()
@@ -255,6 +309,8 @@ def run_variant(rank, world, args, V, steps, warmup, devices=None):
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, gr, last, begin, count, args.seed)
     # node-level result: all-reduce (sum) the int64 counters over RCCL; max of the clocks
     cuda = f"cuda:{dev}"
     total = rdist.allreduce_summary(last.summary, device=cuda)
@@ -309,13 +365,16 @@ def main(argv=None):
     if launched:
         dist.init_process_group("nccl", device_id=torch.device(f"cuda:{dev}"))
     n_gpus = len(devices) if devices else world
-    head = run_variant(rank, world, args, args.V, args.steps, args.warmup, devices)
-    variants = {}
-    for v in [int(x) for x in args.variants.split(",") if x]:
-        r = run_variant(rank, world, args, v, max(1, args.steps // 2), 1, devices)
-        pr = r["summary"].process_rounds * max(1, args.steps // 2)
-        variants[f"V={v}"] = {"value": pr / r["dt"], "kernel_ms": r["kernel_s"] * 1e3,
-                              "violations": psync.BatchResult(psync.OTR(), args.rounds, r["summary"]).violations()}
+    head = run_variant(rank, world, args, args.V, args.steps, args.warmup, devices, args.dump_outputs)
+    variants = None
+    if args.full:
+        variants = {}
+        for v in [int(x) for x in args.variants.split(",") if x]:
+            r = run_variant(rank, world, args, v, max(1, args.steps // 2), 1, devices)
+            pr = r["summary"].process_rounds * max(1, args.steps // 2)
+            variants[f"V={v}"] = {"value": pr / r["dt"], "kernel_ms": r["kernel_s"] * 1e3,
+                                  "violations": psync.BatchResult(psync.OTR(), args.rounds,
+                                                                  r["summary"]).violations()}
     if rank == 0:
         s = head["summary"]
         steps = args.steps
@@ -336,6 +395,7 @@ def main(argv=None):
             "n_gpus": n_gpus,
             "steps": steps,
             "warmup": args.warmup,
+            "full": args.full,  # false: variants / profile roofline / cpu_baseline were not run (null)
             "ms_per_step": head["dt"] / steps * 1e3,
             "higher_is_better": True,
             "scaling": "weak",
@@ -387,7 +447,7 @@ def main(argv=None):
             },
             "variants": variants,
         }
-        prof = pmc_profile(args)
+        prof = pmc_profile(args) if args.full else None
         if prof is not None:
             src, d, same = prof
             rl = out["roofline"]
@@ -426,7 +486,7 @@ def main(argv=None):
                 # counters of another build say nothing about this one's rates
                 rl["stale_profile"] = "profile taken on a different libpsg.so: achieved / frac / traffic " \
                                       "left null; profile_issue_utilization is that build's own figure"
-        if not args.no_cpu_baseline and n_gpus == 1:  # the host baseline is an N = 1 figure
+        if args.full and not args.no_cpu_baseline and n_gpus == 1:  # the host baseline is an N = 1 figure
             out["cpu_baseline"] = cpu_baseline(head["cfg"], args.cpu_seconds)
         else:
             out["cpu_baseline"] = None

@@ -23,9 +23,9 @@ step() {  # step <name> <timeout-s> <cmd...>
 
 sha256sum "$ROOT/round_amd/libpsg.so" | cut -d' ' -f1 > "$OUT/lib_sha256.txt"
 B="python3 $ROOT/bench.py"
-SMALL="--steps 2 --warmup 1 --variants= --no-cpu-baseline"
+SMALL="--steps 2 --warmup 1"  # plain runs: the headline series only
 
-step bench_default 500 $B
+step bench_default 500 $B --full
 step kt 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt" -o run -- $B $SMALL
 step pmc_fetch 400 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$OUT/pmc_fetch" -o run -- $B $SMALL
 step pmc_write 400 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d "$OUT/pmc_write" -o run -- $B $SMALL

@@ -97,6 +97,21 @@ def test_parallelism_label_states_whether_rccl_ran():
     assert "RCCL" not in dl and "[0, 1]" in dl
 
 
+def test_plain_run_is_the_default():
+    """--full (variants, profile roofline, CPU baseline) and --dump-outputs are off unless asked for."""
+    a = _args("--gpus", "1", "--steps", "7", "--warmup", "3")
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, "", 7, 3)
+    a = _args("--full", "--dump-outputs", "some/dir")
+    assert a.full and a.dump_outputs == "some/dir"
+
+
+def test_digest_limbs_are_exact():
+    for v in (0, 1, -1, 0x0123456789ABCDEF, -(1 << 63)):
+        limbs = bench._limbs16(v)
+        assert all(0 <= x < 1 << 16 for x in limbs)
+        assert sum(x << (16 * k) for k, x in enumerate(limbs)) == v & ((1 << 64) - 1)
+
+
 def test_pmc_profile_prefers_the_profile_of_this_build(monkeypatch, tmp_path):
     """A profile taken on the running libpsg.so wins over a later-named one of another build."""
     a = _args()

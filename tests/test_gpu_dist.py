@@ -79,8 +79,7 @@ def test_bench_under_torchrun_world1():
     port = _free_port()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
            "--master-addr=127.0.0.1", f"--master-port={port}", os.path.join(ROOT, "bench.py"),
-           "--gpus", "1", "--steps", "2", "--warmup", "1", "--instances", "200000", "--variants=",
-           "--no-cpu-baseline"]
+           "--gpus", "1", "--steps", "2", "--warmup", "1", "--instances", "200000"]
     env = dict(os.environ, OMP_NUM_THREADS="1")
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=110)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -99,7 +98,7 @@ def test_bench_device_list_two_devices():
     from round_amd import psync
     per = 100_000
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--device-list", "0,0", "--steps", "2", "--warmup", "1",
-           "--instances", str(per), "--variants=", "--no-cpu-baseline"]
+           "--instances", str(per)]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=110)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
