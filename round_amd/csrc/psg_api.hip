@@ -13,6 +13,7 @@
 #include <new>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "../../include/psg.h"
@@ -46,23 +47,72 @@ hipError_t launch_gen_init(uint64_t inst_begin, uint64_t count, int n, int alg, 
 
 using namespace psg;
 
-struct psg_ctx {
+// Owning device buffer: pointer + capacity in elements.
+template <class T>
+struct DevBuf {
+  T* p = nullptr;
+  uint64_t cap = 0;
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept { *this = std::move(o); }
+  DevBuf& operator=(DevBuf&& o) noexcept {  // (what std::swap of two generations is made of)
+    std::swap(p, o.p);
+    std::swap(cap, o.cap);
+    return *this;
+  }
+  ~DevBuf() { release(); }
+  operator T*() const { return p; }
+  // Room for count elements: nothing when they already fit, else free and reallocate (the contents go).
+  hipError_t grow(uint64_t count) {
+    if (count <= cap) return hipSuccess;
+    release();
+    const hipError_t e = hipMalloc(&p, sizeof(T) * count);
+    if (e == hipSuccess) cap = count;
+    else p = nullptr;
+    return e;
+  }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+  }
+};
+
+// Every device allocation of a context (psg_destroy frees them as one).
+struct psg_buffers {
+  DevBuf<int32_t> d_init;
+  DevBuf<double> d_init_f64;  // EpsilonConsensus: staged host Double inputs
+  DevBuf<double> d_dec_f64;
+  DevBuf<double> d_rec_f64;   // fetch path: [k][n][2] (decision, final x)
+  DevBuf<int32_t> d_trace;    // psg_run_batch_spec: state trace of one chunk
+  DevBuf<unsigned long long> d_vm_counters;
+  DevBuf<int32_t> d_vm_err;
+  DevBuf<int32_t> d_prog;     // code | slot_entry | slot_flags
+  // explicit schedule (psg_load_schedule): ho[inst][k][p][W], crash[inst][p]
+  DevBuf<uint64_t> d_ho;
+  DevBuf<int32_t> d_crash;
+  // search populations (psg_population_*): second buffers of the HO sets / inputs
+  DevBuf<uint64_t> d_ho2;
+  DevBuf<int32_t> d_init2;
+  DevBuf<uint32_t> d_parent;
+  DevBuf<uint8_t> d_op;
+  DevBuf<int32_t> d_dec;
+  DevBuf<uint8_t> d_dround;
+  DevBuf<psg_instance_summary> d_inst;
+  DevBuf<unsigned long long> d_counters;
+  DevBuf<uint64_t> d_ids;
+  DevBuf<psg_process_record> d_rec;
+  // packed KSet (n > 64): state handed from the general-round kernel to the uniform-t tail
+  // kernel, per batch row a header word, 64 lane words and n decisions (psg_kset.hip)
+  DevBuf<uint64_t> d_hand;
+};
+
+struct psg_ctx : psg_buffers {
   psg_config cfg;
   int W = 1;
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   uint64_t cap = 0;
-  int32_t* d_init = nullptr;
-  double* d_init_f64 = nullptr;  // EpsilonConsensus: staged host Double inputs
   bool init_f64_host = false;    // false: seeded Doubles generated inside the round kernel
-  double* d_dec_f64 = nullptr;
-  double* d_rec_f64 = nullptr;   // fetch path: [k][n][2] (decision, final x)
-  int32_t* d_trace = nullptr;    // psg_run_batch_spec: state trace of one chunk
-  uint64_t trace_cap = 0;        // instances the trace buffer holds
-  unsigned long long* d_vm_counters = nullptr;
-  int32_t* d_vm_err = nullptr;
-  int32_t* d_prog = nullptr;     // code | slot_entry | slot_flags
-  size_t prog_cap = 0;
   std::string module_path;       // native Spec code object currently loaded
   hipModule_t module = nullptr;
   hipFunction_t native_fn = nullptr;
@@ -72,29 +122,10 @@ struct psg_ctx {
   bool staged_host = false;      // the staged rows came from the host (else seeded values)
   uint64_t staged_begin = 0, staged_count = 0;
   // explicit schedule (psg_load_schedule)
-  uint64_t* d_ho = nullptr;
-  int32_t* d_crash = nullptr;
-  uint64_t ho_cap = 0;  // instances d_ho / d_crash hold
   bool ho_loaded = false, ho_has_crash = false;
   uint64_t ho_begin = 0, ho_count = 0;
-  // search populations (psg_population_*): second buffers of the HO sets / inputs
-  uint64_t* d_ho2 = nullptr;
-  int32_t* d_init2 = nullptr;
-  uint32_t* d_parent = nullptr;
-  uint8_t* d_op = nullptr;
-  uint64_t pop_cap = 0;
-  int32_t* d_dec = nullptr;
-  uint8_t* d_dround = nullptr;
-  psg_instance_summary* d_inst = nullptr;
-  unsigned long long* d_counters = nullptr;
-  uint64_t* d_ids = nullptr;
-  psg_process_record* d_rec = nullptr;
-  uint64_t fetch_cap = 0;
   uint64_t last_count = 0;
   int grid_max = 0;  // resident blocks for the algorithm's kernel
-  // packed KSet (n > 64): state handed from the general-round kernel to the uniform-t tail
-  // kernel, per batch row a header word, 64 lane words and n decisions (psg_kset.hip)
-  uint64_t* d_hand = nullptr;
   std::string err;
   // multi-device context (cfg.n_devices > 0): one single-device context per listed
   // device; every call splits its range into contiguous slices, one per device
@@ -103,21 +134,6 @@ struct psg_ctx {
 
 static thread_local std::string g_create_err;
 
-static int n_checks(int alg) {
-  switch (alg) {
-    case PSG_ALG_OTR: return 8;
-    case PSG_ALG_LAST_VOTING: return 7;
-    case PSG_ALG_BENOR: return 5;
-    case PSG_ALG_FLOODMIN: return 2;
-    case PSG_ALG_KSET: return 2;
-    case PSG_ALG_OTR2: return 8;
-    case PSG_ALG_SLV: return 2;
-    case PSG_ALG_KSET_ES: return 2;
-    case PSG_ALG_EPSILON: return 3;
-  }
-  return 0;
-}
-
 static const char* const k_names_otr[] = {"Safety", "Invariant0", "Invariant1", "Invariant2",
                                           "Agreement", "Validity", "Integrity", "Irrevocability"};
 static const char* const k_names_lv[] = {"Safety", "Invariant0", "Invariant1", "Agreement",
@@ -125,6 +141,112 @@ static const char* const k_names_lv[] = {"Safety", "Invariant0", "Invariant1", "
 static const char* const k_names_benor[] = {"Safety", "Invariant0", "Agreement", "Irrevocability", "SafetyPredicate"};
 static const char* const k_names_k[] = {"KAgreement", "KValidity"};
 static const char* const k_names_eps[] = {"EpsAgreement", "EpsValidity", "SafetyPredicate"};
+
+struct CheckNames {
+  const char* const* name;
+  int count;
+  constexpr CheckNames() : name(nullptr), count(0) {}
+  template <int N>
+  constexpr CheckNames(const char* const (&a)[N]) : name(a), count(N) {}
+};
+
+// Everything the host layer knows about one algorithm; k_algs is indexed by PSG_ALG_*.
+struct AlgRow {
+  const char* class_name;  // the reference's class
+  CheckNames checks;
+  void (*defaults)(psg_config& cfg, int n);          // on top of psg_config_default's common part
+  const char* (*invalid)(const psg_config& cfg);     // the parameter rule the config breaks, or null
+  hipError_t (*launch)(const KArgs& a, int W, int grid, hipStream_t s);
+  const void* (*kernel)(int W);                      // the variant the resident-block count is taken from
+};
+
+static const char* need_value_range(const psg_config& c) { return c.value_range < 1 ? "value_range must be >= 1" : nullptr; }
+
+static void lv_defaults(psg_config& c, int n) {
+  c.value_range = (1 << 15) - 1;
+  c.sched.drop_log2 = 4;
+  c.sched.good_p32 = 0;
+  c.sched.crash_fmax = (n - 1) / 2;
+}
+
+static void crash_stop_defaults(psg_config& c, int rounds, int fmax) {  // loss-free links, at most fmax crashes
+  c.param = 2;
+  c.rounds = rounds;
+  c.value_range = 1000000;
+  c.sched.drop_log2 = 0;
+  c.sched.good_p32 = 0;
+  c.sched.crash_fmax = fmax;
+}
+
+static const char* otr_invalid(const psg_config& c) {
+  if (const char* m = need_value_range(c)) return m;
+  return c.param < 1 ? "OTR needs afterDecision >= 1" : nullptr;
+}
+
+static const AlgRow k_algs[] = {
+    {},  // (PSG_ALG_* start at 1)
+    {"example.OTR", k_names_otr, [](psg_config& c, int) { c.param = 2; /* afterDecision (Otr.scala:89) */ }, otr_invalid,
+     launch_otr, otr_kernel_ptr},
+    {"example.LastVoting", k_names_lv, lv_defaults, need_value_range, launch_lv, lv_kernel_ptr},
+    {"example.FloodMin", k_names_k, [](psg_config& c, int) { crash_stop_defaults(c, 4, 2); },
+     [](const psg_config& c) {
+       if (const char* m = need_value_range(c)) return m;
+       return c.param < 0 ? "FloodMin needs f >= 0" : nullptr;
+     },
+     launch_floodmin, floodmin_kernel_ptr},
+    {"example.KSetAgreement", k_names_k, [](psg_config& c, int) { crash_stop_defaults(c, 16, 1); },
+     [](const psg_config& c) {
+       if (const char* m = need_value_range(c)) return m;
+       return c.param < 1 ? "KSetAgreement needs k >= 1" : nullptr;
+     },
+     launch_kset, kset_kernel_ptr},
+    {"example.BenOr", k_names_benor,
+     [](psg_config& c, int n) {
+       c.rounds = 64;
+       c.value_range = 2;
+       c.sched.drop_log2 = 2;
+       c.sched.good_p32 = 0;
+       c.sched.ho_min = n / 2;
+     },
+     [](const psg_config&) -> const char* { return nullptr; }, launch_benor, benor_kernel_ptr},
+    {"example.OTR2", k_names_otr, [](psg_config& c, int) { c.param = 2; /* afterDecision (Otr2.scala:69) */ }, otr_invalid,
+     launch_otr2, otr2_kernel_ptr},
+    {"example.ShortLastVoting", k_names_k,
+     [](psg_config& c, int n) {
+       lv_defaults(c, n);
+       c.rounds = 30;
+     },
+     need_value_range, launch_slv, slv_kernel_ptr},
+    {"example.KSetEarlyStopping", k_names_k,
+     [](psg_config& c, int) {  // t = 2, k = 2 (KSetEarlyStopping.scala:63-67)
+       crash_stop_defaults(c, 3, 2);
+       c.param2 = 2;
+     },
+     [](const psg_config& c) {
+       if (const char* m = need_value_range(c)) return m;
+       return c.param < 0 || c.param2 < 1 ? "KSetEarlyStopping needs t >= 0 and k >= 1" : nullptr;
+     },
+     launch_kset_es, kset_es_kernel_ptr},
+    {"example.EpsilonConsensus", k_names_eps,
+     [](psg_config& c, int n) {  // f = 1, epsilon = 0.1 (Epsilon.scala:83-89)
+       c.param = 1;
+       c.real_param = 0.1;
+       c.rounds = 12;
+       c.sched.drop_log2 = 4;
+       c.sched.good_p32 = 0;
+       c.sched.ho_min = n - 2;  // |HO(p)| >= n - f
+     },
+     [](const psg_config& c) {
+       return c.param < 1 || !(c.real_param > 0.0) ? "EpsilonConsensus needs f >= 1 and epsilon > 0" : nullptr;
+     },
+     launch_epsilon, epsilon_kernel_ptr},
+};
+
+constexpr int k_alg_rows = (int)(sizeof(k_algs) / sizeof(k_algs[0]));
+static_assert(k_alg_rows == PSG_ALG_EPSILON + 1, "one row per PSG_ALG_*, in the enum's order");
+
+// The row of an algorithm id; null: unknown algorithm.
+static const AlgRow* alg_row(int alg) { return alg > 0 && alg < k_alg_rows ? &k_algs[alg] : nullptr; }
 
 static int fail(psg_ctx* c, int code, const std::string& msg) {
   if (c) c->err = msg;
@@ -175,36 +297,6 @@ static void print_timers(const unsigned long long* host) {
   std::fprintf(stderr, "\n");
 }
 
-static hipError_t launch_alg(const psg_ctx* c, const KArgs& a, int grid) {
-  switch (c->cfg.alg) {
-    case PSG_ALG_OTR: return launch_otr(a, c->W, grid, c->stream);
-    case PSG_ALG_LAST_VOTING: return launch_lv(a, c->W, grid, c->stream);
-    case PSG_ALG_FLOODMIN: return launch_floodmin(a, c->W, grid, c->stream);
-    case PSG_ALG_KSET: return launch_kset(a, c->W, grid, c->stream);
-    case PSG_ALG_BENOR: return launch_benor(a, c->W, grid, c->stream);
-    case PSG_ALG_OTR2: return launch_otr2(a, c->W, grid, c->stream);
-    case PSG_ALG_SLV: return launch_slv(a, c->W, grid, c->stream);
-    case PSG_ALG_KSET_ES: return launch_kset_es(a, c->W, grid, c->stream);
-    case PSG_ALG_EPSILON: return launch_epsilon(a, c->W, grid, c->stream);
-  }
-  return hipErrorInvalidValue;
-}
-
-static const void* kernel_ptr(int alg, int W) {
-  switch (alg) {
-    case PSG_ALG_OTR: return otr_kernel_ptr(W);
-    case PSG_ALG_LAST_VOTING: return lv_kernel_ptr(W);
-    case PSG_ALG_FLOODMIN: return floodmin_kernel_ptr(W);
-    case PSG_ALG_KSET: return kset_kernel_ptr(W);
-    case PSG_ALG_BENOR: return benor_kernel_ptr(W);
-    case PSG_ALG_OTR2: return otr2_kernel_ptr(W);
-    case PSG_ALG_SLV: return slv_kernel_ptr(W);
-    case PSG_ALG_KSET_ES: return kset_es_kernel_ptr(W);
-    case PSG_ALG_EPSILON: return epsilon_kernel_ptr(W);
-  }
-  return nullptr;
-}
-
 static KArgs make_args(const psg_ctx* c) {
   KArgs a;
   std::memset(&a, 0, sizeof(a));
@@ -248,31 +340,74 @@ static int check_sched_range(psg_ctx* c, uint64_t begin, uint64_t count) {
   return PSG_OK;
 }
 
-static int groups_per_block(int W) { return W == 1 ? 4 : 1; }
+// Block geometry of the round kernels (Geometry<W>, psg_device.hpp) for the context's W.
+static int threads_per_block(int W) { return with_w(W, 0, [](auto w) { return Geometry<w()>::kThreads; }); }
+static int groups_per_block(int W) { return with_w(W, 1, [](auto w) { return Geometry<w()>::kGroups; }); }
 
-static int run_kernel(psg_ctx* c, KArgs& a, uint64_t count, psg_summary* out, bool timed) {
+static bool is_staged(const psg_ctx* c, uint64_t begin, uint64_t count) {
+  return c->staged && c->staged_begin == begin && c->staged_count == count;
+}
+
+static void set_staged(psg_ctx* c, uint64_t begin, uint64_t count, bool from_host) {
+  c->staged = true;
+  c->staged_host = from_host;
+  c->staged_begin = begin;
+  c->staged_count = count;
+}
+
+// Counters of one launch -> summary. The Spec VM's counters hold the check slots and the termination
+// histogram only (checks_only), which replace those of the round kernel's built-in checks.
+static void fill_summary(psg_summary& s, const unsigned long long* host, int rounds, bool checks_only) {
+  for (int i = 0; i < PSG_MAX_CHECKS; ++i) s.fail_count[i] = (int64_t)host[C_FAIL + i];
+  for (int i = 0; i < rounds + 2; ++i) s.term_hist[i] = (int64_t)host[C_HIST + i];
+  if (checks_only) return;
+  s.active_process_rounds = (int64_t)host[C_ACTIVE];
+  s.live_instance_rounds = (int64_t)host[C_LIVE];
+  s.decided_processes = (int64_t)host[C_DECIDED];
+  s.digest = (int64_t)host[C_DIGEST];
+}
+
+// acc += p, except kernel_ns: devices run side by side, chunks one after the other (the callers' choice)
+static void summary_add(psg_summary& acc, const psg_summary& p) {
+  acc.instances += p.instances;
+  acc.process_rounds += p.process_rounds;
+  acc.active_process_rounds += p.active_process_rounds;
+  acc.live_instance_rounds += p.live_instance_rounds;
+  for (int i = 0; i < PSG_MAX_CHECKS; ++i) acc.fail_count[i] += p.fail_count[i];
+  acc.decided_processes += p.decided_processes;
+  acc.digest = (int64_t)((uint64_t)acc.digest + (uint64_t)p.digest);
+  for (int i = 0; i < PSG_MAX_ROUNDS + 2; ++i) acc.term_hist[i] += p.term_hist[i];
+}
+
+// One launch of the round kernel over `count` instances and its readback: zero the counters, launch
+// (timed: between the context's events), copy the counters back, synchronise, fill *out (if given).
+// The kernel is the algorithm's own (k_algs), or a fused Spec module's `fused` of at most fused_grid blocks.
+static int run_kernel(psg_ctx* c, KArgs& a, uint64_t count, psg_summary* out, bool timed, hipFunction_t fused = nullptr,
+                      uint64_t fused_grid = 0) {
   const int G = groups_per_block(c->W);
-  uint64_t want = (count + G - 1) / G;
-  int grid = (int)std::min<uint64_t>(want, (uint64_t)c->grid_max);
-  if (grid < 1) grid = 1;
+  const uint64_t want = (count + G - 1) / G;
+  const int grid = (int)std::max<uint64_t>(1, std::min<uint64_t>(want, fused ? fused_grid : (uint64_t)c->grid_max));
   HIPCHK(c, hipMemsetAsync(c->d_counters, 0, sizeof(unsigned long long) * NCOUNTERS_ALLOC, c->stream));
   if (timed) HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-  HIPCHK(c, launch_alg(c, a, grid));
+  if (fused) {
+    void* params[] = {&a};
+    HIPCHK(c, hipModuleLaunchKernel(fused, (unsigned)grid, 1, 1, (unsigned)threads_per_block(c->W), 1, 1, 0, c->stream,
+                                    params, nullptr));
+  } else {
+    HIPCHK(c, alg_row(c->cfg.alg)->launch(a, c->W, grid, c->stream));
+  }
   if (timed) HIPCHK(c, hipEventRecord(c->ev1, c->stream));
   unsigned long long host[NCOUNTERS_ALLOC];
   HIPCHK(c, hipMemcpyAsync(host, c->d_counters, sizeof(host), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  // (a fused module shows its timers when it was compiled with -DPSG_PHASE_TIMERS=1 too:
+  // formula.compile_native(defines=...))
   if (PSG_PHASE_TIMERS && std::getenv("PSG_PHASE_TIMERS")) print_timers(host);
   if (out) {
     std::memset(out, 0, sizeof(*out));
     out->instances = (int64_t)count;
     out->process_rounds = (int64_t)count * c->cfg.n * c->cfg.rounds;
-    out->active_process_rounds = (int64_t)host[C_ACTIVE];
-    out->live_instance_rounds = (int64_t)host[C_LIVE];
-    for (int i = 0; i < PSG_MAX_CHECKS; ++i) out->fail_count[i] = (int64_t)host[C_FAIL + i];
-    out->decided_processes = (int64_t)host[C_DECIDED];
-    out->digest = (int64_t)host[C_DIGEST];
-    for (int i = 0; i < c->cfg.rounds + 2; ++i) out->term_hist[i] = (int64_t)host[C_HIST + i];
+    fill_summary(*out, host, c->cfg.rounds, false);
     if (timed) {
       float ms = 0.f;
       HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
@@ -327,173 +462,79 @@ int psg_config_default(psg_config* cfg, int32_t alg, int32_t n) {
   cfg->sched.crash_fmax = -1;
   cfg->sched.ho_min = -1;
   cfg->sched.self_bit = 1;
-  switch (alg) {
-    case PSG_ALG_OTR: cfg->param = 2; break;  // afterDecision (Otr.scala:89)
-    case PSG_ALG_LAST_VOTING:
-      cfg->value_range = (1 << 15) - 1;
-      cfg->sched.drop_log2 = 4;
-      cfg->sched.good_p32 = 0;
-      cfg->sched.crash_fmax = (n - 1) / 2;
-      break;
-    case PSG_ALG_FLOODMIN:
-      cfg->param = 2;
-      cfg->rounds = 4;
-      cfg->value_range = 1000000;
-      cfg->sched.drop_log2 = 0;
-      cfg->sched.good_p32 = 0;
-      cfg->sched.crash_fmax = 2;
-      break;
-    case PSG_ALG_KSET:
-      cfg->param = 2;
-      cfg->rounds = 16;
-      cfg->value_range = 1000000;
-      cfg->sched.drop_log2 = 0;
-      cfg->sched.good_p32 = 0;
-      cfg->sched.crash_fmax = 1;
-      break;
-    case PSG_ALG_BENOR:
-      cfg->rounds = 64;
-      cfg->value_range = 2;
-      cfg->sched.drop_log2 = 2;
-      cfg->sched.good_p32 = 0;
-      cfg->sched.ho_min = n / 2;
-      break;
-    case PSG_ALG_OTR2: cfg->param = 2; break;  // afterDecision (Otr2.scala:69)
-    case PSG_ALG_SLV:
-      cfg->rounds = 30;
-      cfg->value_range = (1 << 15) - 1;
-      cfg->sched.drop_log2 = 4;
-      cfg->sched.good_p32 = 0;
-      cfg->sched.crash_fmax = (n - 1) / 2;
-      break;
-    case PSG_ALG_EPSILON:  // f = 1, epsilon = 0.1 (Epsilon.scala:83-89)
-      cfg->param = 1;
-      cfg->real_param = 0.1;
-      cfg->rounds = 12;
-      cfg->sched.drop_log2 = 4;
-      cfg->sched.good_p32 = 0;
-      cfg->sched.ho_min = n - 2;  // |HO(p)| >= n - f
-      break;
-    case PSG_ALG_KSET_ES:  // t = 2, k = 2 (KSetEarlyStopping.scala:63-67)
-      cfg->param = 2;
-      cfg->param2 = 2;
-      cfg->rounds = 3;
-      cfg->value_range = 1000000;
-      cfg->sched.drop_log2 = 0;
-      cfg->sched.good_p32 = 0;
-      cfg->sched.crash_fmax = 2;
-      break;
-    default: return PSG_EINVAL;
-  }
+  const AlgRow* row = alg_row(alg);
+  if (!row) return PSG_EINVAL;
+  row->defaults(*cfg, n);
   return PSG_OK;
 }
 
-int psg_check_count(int32_t alg) { return n_checks(alg); }
+int psg_check_count(int32_t alg) {
+  const AlgRow* row = alg_row(alg);
+  return row ? row->checks.count : 0;
+}
 
 const char* psg_check_name(int32_t alg, int32_t slot) {
-  if (slot < 0 || slot >= n_checks(alg)) return nullptr;
-  switch (alg) {
-    case PSG_ALG_OTR:
-    case PSG_ALG_OTR2: return k_names_otr[slot];
-    case PSG_ALG_LAST_VOTING: return k_names_lv[slot];
-    case PSG_ALG_BENOR: return k_names_benor[slot];
-    case PSG_ALG_EPSILON: return k_names_eps[slot];
-    default: return k_names_k[slot];
-  }
+  return slot >= 0 && slot < psg_check_count(alg) ? alg_row(alg)->checks.name[slot] : nullptr;
 }
 
 int psg_alg_from_class(const char* name) {
   if (!name) return PSG_EINVAL;
-  static const struct { const char* n; int id; } tab[] = {
-      {"example.OTR", PSG_ALG_OTR}, {"example.LastVoting", PSG_ALG_LAST_VOTING},
-      {"example.FloodMin", PSG_ALG_FLOODMIN}, {"example.KSetAgreement", PSG_ALG_KSET},
-      {"example.BenOr", PSG_ALG_BENOR}, {"example.OTR2", PSG_ALG_OTR2},
-      {"example.ShortLastVoting", PSG_ALG_SLV}, {"example.KSetEarlyStopping", PSG_ALG_KSET_ES},
-      {"example.EpsilonConsensus", PSG_ALG_EPSILON}};
-  for (auto& t : tab)
-    if (std::strcmp(t.n, name) == 0) return t.id;
+  for (int alg = 1; const AlgRow* row = alg_row(alg); ++alg)
+    if (std::strcmp(row->class_name, name) == 0) return alg;
   return PSG_EINVAL;
 }
 
 const char* psg_create_error(void) { return g_create_err.c_str(); }
 
+// Both selftests run on the null stream of `device`; their scratch buffers free themselves.
+static int selftest_device(int32_t device) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return PSG_ENODEV;
+  return hipSetDevice(device) == hipSuccess ? PSG_OK : PSG_ENODEV;
+}
+
 int psg_selftest_map_head(int32_t device, const uint64_t* sets, int32_t count, int32_t tiebreak, int32_t* out_first) {
   if (!sets || !out_first || count < 0) return PSG_EINVAL;
   if (tiebreak != PSG_TIE_CHAMP && tiebreak != PSG_TIE_MIN_PID) return PSG_EINVAL;
   if (count == 0) return PSG_OK;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return PSG_ENODEV;
-  if (hipSetDevice(device) != hipSuccess) return PSG_ENODEV;
-  uint64_t* d_sets = nullptr;
-  int32_t* d_out = nullptr;
-  int rc = PSG_OK;
-  if (hipMalloc(&d_sets, sizeof(uint64_t) * count) != hipSuccess ||
-      hipMalloc(&d_out, sizeof(int32_t) * count) != hipSuccess) {
-    rc = PSG_ENOMEM;
-  } else if (hipMemcpy(d_sets, sets, sizeof(uint64_t) * count, hipMemcpyHostToDevice) != hipSuccess ||
-             launch_champ_selftest(d_sets, count, tiebreak, d_out, nullptr) != hipSuccess ||
-             hipMemcpy(out_first, d_out, sizeof(int32_t) * count, hipMemcpyDeviceToHost) != hipSuccess) {
-    rc = PSG_EIO;
-  }
-  if (d_sets) (void)hipFree(d_sets);
-  if (d_out) (void)hipFree(d_out);
-  return rc;
+  if (int rc = selftest_device(device)) return rc;
+  DevBuf<uint64_t> d_sets;
+  DevBuf<int32_t> d_out;
+  if (d_sets.grow(count) != hipSuccess || d_out.grow(count) != hipSuccess) return PSG_ENOMEM;
+  if (hipMemcpy(d_sets, sets, sizeof(uint64_t) * count, hipMemcpyHostToDevice) != hipSuccess ||
+      launch_champ_selftest(d_sets, count, tiebreak, d_out, nullptr) != hipSuccess ||
+      hipMemcpy(out_first, d_out, sizeof(int32_t) * count, hipMemcpyDeviceToHost) != hipSuccess)
+    return PSG_EIO;
+  return PSG_OK;
 }
 
 int psg_selftest_bitset(int32_t device, int32_t W, const int32_t* ops, int32_t n_ops, int32_t* out, int32_t n_out) {
   if (!ops || !out || n_ops < 0 || n_out < 0 || W < 1 || W > 4) return PSG_EINVAL;
   if (n_ops == 0) return PSG_OK;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return PSG_ENODEV;
-  if (hipSetDevice(device) != hipSuccess) return PSG_ENODEV;
-  int32_t *d_ops = nullptr, *d_out = nullptr;
-  int rc = PSG_OK;
-  const size_t ob = sizeof(int32_t) * (n_out > 0 ? n_out : 1);
-  if (hipMalloc(&d_ops, sizeof(int32_t) * 2 * (size_t)n_ops) != hipSuccess || hipMalloc(&d_out, ob) != hipSuccess) {
-    rc = PSG_ENOMEM;
-  } else if (hipMemcpy(d_ops, ops, sizeof(int32_t) * 2 * (size_t)n_ops, hipMemcpyHostToDevice) != hipSuccess ||
-             hipMemset(d_out, 0xFF, ob) != hipSuccess) {
-    rc = PSG_EIO;
-  } else {
-    switch (W) {
-      case 1: hipLaunchKernelGGL(bitset_selftest_kernel<1>, dim3(1), dim3(64), 0, nullptr, d_ops, n_ops, d_out, n_out); break;
-      case 2: hipLaunchKernelGGL(bitset_selftest_kernel<2>, dim3(1), dim3(64), 0, nullptr, d_ops, n_ops, d_out, n_out); break;
-      case 3: hipLaunchKernelGGL(bitset_selftest_kernel<3>, dim3(1), dim3(64), 0, nullptr, d_ops, n_ops, d_out, n_out); break;
-      default: hipLaunchKernelGGL(bitset_selftest_kernel<4>, dim3(1), dim3(64), 0, nullptr, d_ops, n_ops, d_out, n_out); break;
-    }
-    if (hipGetLastError() != hipSuccess ||
-        (n_out > 0 && hipMemcpy(out, d_out, sizeof(int32_t) * n_out, hipMemcpyDeviceToHost) != hipSuccess))
-      rc = PSG_EIO;
-  }
-  if (d_ops) (void)hipFree(d_ops);
-  if (d_out) (void)hipFree(d_out);
-  return rc;
+  if (int rc = selftest_device(device)) return rc;
+  DevBuf<int32_t> d_ops, d_out;
+  if (d_ops.grow(2 * (uint64_t)n_ops) != hipSuccess || d_out.grow(n_out > 0 ? n_out : 1) != hipSuccess) return PSG_ENOMEM;
+  if (hipMemcpy(d_ops, ops, sizeof(int32_t) * 2 * (size_t)n_ops, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemset(d_out, 0xFF, sizeof(int32_t) * d_out.cap) != hipSuccess)
+    return PSG_EIO;
+  const hipError_t e = with_w(W, hipErrorInvalidValue, [&](auto w) {
+    hipLaunchKernelGGL(bitset_selftest_kernel<w()>, dim3(1), dim3(64), 0, nullptr, (const int32_t*)d_ops, n_ops,
+                       (int32_t*)d_out, n_out);
+    return hipGetLastError();
+  });
+  if (e != hipSuccess || (n_out > 0 && hipMemcpy(out, d_out, sizeof(int32_t) * n_out, hipMemcpyDeviceToHost) != hipSuccess))
+    return PSG_EIO;
+  return PSG_OK;
 }
 
 static int validate(const psg_config* cfg, std::string& m) {
   if (!cfg) { m = "null config"; return PSG_EINVAL; }
   if (cfg->abi_version != PSG_ABI_VERSION) { m = "ABI version mismatch"; return PSG_EINVAL; }
-  if (cfg->alg < PSG_ALG_OTR || cfg->alg > PSG_ALG_EPSILON) { m = "unknown algorithm"; return PSG_EINVAL; }
+  const AlgRow* row = alg_row(cfg->alg);
+  if (!row) { m = "unknown algorithm"; return PSG_EINVAL; }
   if (cfg->n < 1 || cfg->n > PSG_MAX_N) { m = "n out of range 1..256"; return PSG_EINVAL; }
   if (cfg->rounds < 1 || cfg->rounds > PSG_MAX_ROUNDS) { m = "rounds out of range 1..250"; return PSG_EINVAL; }
-  if (cfg->alg != PSG_ALG_BENOR && cfg->alg != PSG_ALG_EPSILON && cfg->value_range < 1) {
-    m = "value_range must be >= 1";
-    return PSG_EINVAL;
-  }
-  if (cfg->alg == PSG_ALG_EPSILON && (cfg->param < 1 || !(cfg->real_param > 0.0))) {
-    m = "EpsilonConsensus needs f >= 1 and epsilon > 0";
-    return PSG_EINVAL;
-  }
-  if (cfg->alg == PSG_ALG_KSET && cfg->param < 1) { m = "KSetAgreement needs k >= 1"; return PSG_EINVAL; }
-  if (cfg->alg == PSG_ALG_FLOODMIN && cfg->param < 0) { m = "FloodMin needs f >= 0"; return PSG_EINVAL; }
-  if ((cfg->alg == PSG_ALG_OTR || cfg->alg == PSG_ALG_OTR2) && cfg->param < 1) {
-    m = "OTR needs afterDecision >= 1";
-    return PSG_EINVAL;
-  }
-  if (cfg->alg == PSG_ALG_KSET_ES && (cfg->param < 0 || cfg->param2 < 1)) {
-    m = "KSetEarlyStopping needs t >= 0 and k >= 1";
-    return PSG_EINVAL;
-  }
+  if (const char* why = row->invalid(*cfg)) { m = why; return PSG_EINVAL; }
   if (cfg->tiebreak != PSG_TIE_CHAMP && cfg->tiebreak != PSG_TIE_MIN_PID) { m = "bad tiebreak"; return PSG_EINVAL; }
   if (cfg->sched.drop_log2 > 16) { m = "drop_log2 > 16"; return PSG_EINVAL; }
   if (cfg->batch_capacity < 1) { m = "batch_capacity must be >= 1"; return PSG_EINVAL; }
@@ -534,16 +575,18 @@ static int par_subs(psg_ctx* c, F&& f) {
   return PSG_OK;
 }
 
-static void summary_add(psg_summary& acc, const psg_summary& p) {
-  acc.instances += p.instances;
-  acc.process_rounds += p.process_rounds;
-  acc.active_process_rounds += p.active_process_rounds;
-  acc.live_instance_rounds += p.live_instance_rounds;
-  for (int i = 0; i < PSG_MAX_CHECKS; ++i) acc.fail_count[i] += p.fail_count[i];
-  acc.decided_processes += p.decided_processes;
-  acc.digest = (int64_t)((uint64_t)acc.digest + (uint64_t)p.digest);
-  for (int i = 0; i < PSG_MAX_ROUNDS + 2; ++i) acc.term_hist[i] += p.term_hist[i];
-  acc.kernel_ns = std::max(acc.kernel_ns, p.kernel_ns);
+// The slices of the last batch, in device order: f(the device's context, its offset in cells of n)
+template <class F>
+static int each_last_slice(psg_ctx* c, F&& f) {
+  const uint64_t n = (uint64_t)c->cfg.n, nd = c->subs.size();
+  for (size_t d = 0; d < nd; ++d) {
+    uint64_t off, m;
+    split(c->last_count, nd, d, off, m);
+    if (!m) continue;  // an empty slice: the device ran nothing (its own last_count is 0)
+    if (const int rc = f(c->subs[d], off * n))
+      return fail(c, rc, "device " + std::to_string(c->cfg.devices[d]) + ": " + c->subs[d]->err);
+  }
+  return PSG_OK;
 }
 }  // extern "C++"
 
@@ -600,21 +643,19 @@ int psg_create(psg_ctx** out, const psg_config* cfg) {
   CK(hipEventCreate(&c->ev1));
   const uint64_t cells = c->cap * (uint64_t)cfg->n;
   if (cfg->alg == PSG_ALG_EPSILON) {
-    CK(hipMalloc(&c->d_init_f64, sizeof(double) * cells));
-    CK(hipMalloc(&c->d_dec_f64, sizeof(double) * cells));
+    CK(c->d_init_f64.grow(cells));
+    CK(c->d_dec_f64.grow(cells));
   } else {
-    CK(hipMalloc(&c->d_init, sizeof(int32_t) * cells));
+    CK(c->d_init.grow(cells));
   }
-  CK(hipMalloc(&c->d_dec, sizeof(int32_t) * cells));
-  CK(hipMalloc(&c->d_dround, sizeof(uint8_t) * cells));
-  CK(hipMalloc(&c->d_inst, sizeof(psg_instance_summary) * c->cap));
-  CK(hipMalloc(&c->d_counters, sizeof(unsigned long long) * NCOUNTERS_ALLOC));
+  CK(c->d_dec.grow(cells));
+  CK(c->d_dround.grow(cells));
+  CK(c->d_inst.grow(c->cap));
+  CK(c->d_counters.grow(NCOUNTERS_ALLOC));
   if (cfg->alg == PSG_ALG_KSET && c->W > 1)  // 520 + 4n bytes per batch row (psg_kset.hip hand-off)
-    CK(hipMalloc(&c->d_hand, sizeof(uint64_t) * 65 * c->cap + sizeof(int32_t) * cells));
-  const void* kp = kernel_ptr(cfg->alg, c->W);
+    CK(c->d_hand.grow(65 * c->cap + (cells + 1) / 2));  // (the int32 decisions: two to a word)
   int per_cu = 0;
-  const int threads = c->W == 1 ? 256 : 64 * c->W;
-  CK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kp, threads, 0));
+  CK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, alg_row(cfg->alg)->kernel(c->W), threads_per_block(c->W), 0));
   hipDeviceProp_t prop;
   CK(hipGetDeviceProperties(&prop, cfg->device));
   if (per_cu < 1) per_cu = 1;
@@ -636,10 +677,7 @@ static int multi_load_inputs(psg_ctx* c, uint64_t inst_begin, uint64_t count, co
                : psg_load_inputs(c->subs[d], inst_begin + off, m, host_init ? host_init + off * n : nullptr);
   });
   if (rc) return rc;
-  c->staged = true;
-  c->staged_host = f64 ? host_f64 != nullptr : host_init != nullptr;
-  c->staged_begin = inst_begin;
-  c->staged_count = count;
+  set_staged(c, inst_begin, count, f64 ? host_f64 != nullptr : host_init != nullptr);
   return PSG_OK;
 }
 
@@ -664,10 +702,7 @@ int psg_load_inputs(psg_ctx* c, uint64_t inst_begin, uint64_t count, const int32
                               c->stream));
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->staged = true;
-  c->staged_host = host_init != nullptr;
-  c->staged_begin = inst_begin;
-  c->staged_count = count;
+  set_staged(c, inst_begin, count, host_init != nullptr);
   return PSG_OK;
 }
 
@@ -683,10 +718,7 @@ int psg_load_inputs_f64(psg_ctx* c, uint64_t inst_begin, uint64_t count, const d
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
   c->init_f64_host = host_init != nullptr;
-  c->staged = true;
-  c->staged_host = host_init != nullptr;
-  c->staged_begin = inst_begin;
-  c->staged_count = count;
+  set_staged(c, inst_begin, count, host_init != nullptr);
   return PSG_OK;
 }
 
@@ -702,7 +734,7 @@ static int multi_run(psg_ctx* c, uint64_t inst_begin, uint64_t count, const psg_
   }
   if (c->ho_loaded && (inst_begin != c->ho_begin || count != c->ho_count))
     return fail(c, PSG_ERANGE, "a multi-device run under an explicit schedule covers exactly the loaded range");
-  if (!(c->staged && c->staged_begin == inst_begin && c->staged_count == count)) {
+  if (!is_staged(c, inst_begin, count)) {
     const int rc = psg_load_inputs(c, inst_begin, count, nullptr);  // seeded, like a single device
     if (rc) return rc;
   }
@@ -717,23 +749,19 @@ static int multi_run(psg_ctx* c, uint64_t inst_begin, uint64_t count, const psg_
   });
   if (rc) return rc;
   if (out)
-    for (size_t d = 0; d < nd; ++d) summary_add(*out, parts[d]);
+    for (size_t d = 0; d < nd; ++d) {
+      summary_add(*out, parts[d]);
+      out->kernel_ns = std::max(out->kernel_ns, parts[d].kernel_ns);  // the devices ran side by side
+    }
   c->last_count = count;
   return PSG_OK;
 }
 
-int psg_run_batch(psg_ctx* c, uint64_t inst_begin, uint64_t count, psg_summary* out, psg_instance_summary* per_inst) {
-  if (!c) return PSG_EINVAL;
-  if (!c->subs.empty()) return multi_run(c, inst_begin, count, nullptr, out, per_inst);
-  if (count > c->cap) return fail(c, PSG_ERANGE, "inst_count exceeds batch_capacity");
-  if (count == 0) {
-    if (out) std::memset(out, 0, sizeof(*out));
-    c->last_count = 0;
-    return PSG_OK;
-  }
-  if (int rc = check_sched_range(c, inst_begin, count)) return rc;
-  HIPCHK(c, hipSetDevice(c->cfg.device));
-  if (!(c->staged && c->staged_begin == inst_begin && c->staged_count == count)) {
+// One launch over a whole batch from its staged inputs (seeded ones unless the caller staged this
+// range): psg_run_batch, and psg_run_batch_spec through a fused module's round kernel.
+static int run_whole_batch(psg_ctx* c, uint64_t inst_begin, uint64_t count, psg_summary* out,
+                           psg_instance_summary* per_inst, hipFunction_t fused = nullptr, uint64_t fused_grid = 0) {
+  if (!is_staged(c, inst_begin, count)) {
     int rc = psg_load_inputs(c, inst_begin, count, nullptr);
     if (rc) return rc;
   }
@@ -749,13 +777,27 @@ int psg_run_batch(psg_ctx* c, uint64_t inst_begin, uint64_t count, psg_summary* 
   a.out_decision = c->d_dec;
   a.out_dround = c->d_dround;
   a.out_inst = c->d_inst;
-  int rc = run_kernel(c, a, count, out, true);
+  int rc = run_kernel(c, a, count, out, true, fused, fused_grid);
   if (rc) return rc;
   c->last_count = count;
   if (per_inst) {
     HIPCHK(c, hipMemcpy(per_inst, c->d_inst, sizeof(psg_instance_summary) * count, hipMemcpyDeviceToHost));
   }
   return PSG_OK;
+}
+
+int psg_run_batch(psg_ctx* c, uint64_t inst_begin, uint64_t count, psg_summary* out, psg_instance_summary* per_inst) {
+  if (!c) return PSG_EINVAL;
+  if (!c->subs.empty()) return multi_run(c, inst_begin, count, nullptr, out, per_inst);
+  if (count > c->cap) return fail(c, PSG_ERANGE, "inst_count exceeds batch_capacity");
+  if (count == 0) {
+    if (out) std::memset(out, 0, sizeof(*out));
+    c->last_count = 0;
+    return PSG_OK;
+  }
+  if (int rc = check_sched_range(c, inst_begin, count)) return rc;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  return run_whole_batch(c, inst_begin, count, out, per_inst);
 }
 
 static int validate_prog(const psg_spec_program* p, std::string& m) {
@@ -827,18 +869,10 @@ int psg_last_batch_count(const psg_ctx* c, uint64_t* count) {
 
 int psg_copy_decisions(psg_ctx* c, int32_t* decision, int32_t* decision_round) {
   if (!c) return PSG_EINVAL;
-  if (!c->subs.empty()) {  // the last batch's slices, in device order
-    const uint64_t n = (uint64_t)c->cfg.n, nd = c->subs.size();
-    for (size_t d = 0; d < nd; ++d) {
-      uint64_t off, m;
-      split(c->last_count, nd, d, off, m);
-      if (!m) continue;  // an empty slice: the device ran nothing (its own last_count is 0)
-      const int rc = psg_copy_decisions(c->subs[d], decision ? decision + off * n : nullptr,
-                                        decision_round ? decision_round + off * n : nullptr);
-      if (rc) return fail(c, rc, "device " + std::to_string(c->cfg.devices[d]) + ": " + c->subs[d]->err);
-    }
-    return PSG_OK;
-  }
+  if (!c->subs.empty())
+    return each_last_slice(c, [&](psg_ctx* s, uint64_t at) {
+      return psg_copy_decisions(s, decision ? decision + at : nullptr, decision_round ? decision_round + at : nullptr);
+    });
   HIPCHK(c, hipSetDevice(c->cfg.device));
   const uint64_t cells = c->last_count * (uint64_t)c->cfg.n;
   if (decision) HIPCHK(c, hipMemcpy(decision, c->d_dec, sizeof(int32_t) * cells, hipMemcpyDeviceToHost));
@@ -874,13 +908,7 @@ int psg_run_batch_spec(psg_ctx* c, uint64_t inst_begin, uint64_t count, const ps
   const int n = c->cfg.n, R = c->cfg.rounds;
   // program: code | slot_entry | slot_flags
   const size_t words = (size_t)prog->n_words + 2 * (size_t)prog->n_slots;
-  if (words > c->prog_cap) {
-    if (c->d_prog) (void)hipFree(c->d_prog);
-    c->d_prog = nullptr;
-    c->prog_cap = 0;
-    HIPCHK(c, hipMalloc(&c->d_prog, sizeof(int32_t) * words));
-    c->prog_cap = words;
-  }
+  HIPCHK(c, c->d_prog.grow(words));
   HIPCHK(c, hipMemcpy(c->d_prog, prog->code, sizeof(int32_t) * prog->n_words, hipMemcpyHostToDevice));
   HIPCHK(c, hipMemcpy(c->d_prog + prog->n_words, prog->slot_entry, sizeof(int32_t) * prog->n_slots,
                       hipMemcpyHostToDevice));
@@ -918,52 +946,10 @@ int psg_run_batch_spec(psg_ctx* c, uint64_t inst_begin, uint64_t count, const ps
   if (native && (c->ho_loaded ? c->fused_x_fn : c->fused_fn)) {
     // one launch: rounds + Spec from registers (no trace, no chunks)
     hipFunction_t fn = c->ho_loaded ? c->fused_x_fn : c->fused_fn;
-    if (!(c->staged && c->staged_begin == inst_begin && c->staged_count == count)) {
-      int rc = psg_load_inputs(c, inst_begin, count, nullptr);
-      if (rc) return rc;
-    }
-    KArgs a = make_args(c);
-    a.inst_begin = inst_begin;
-    a.count = count;
-    a.init = c->d_init;
-    a.out_decision = c->d_dec;
-    a.out_dround = c->d_dround;
-    a.out_inst = c->d_inst;
-    const int threads = c->W == 1 ? 256 : 64 * c->W;
     int per_cu = 0, cus = 0;
-    HIPCHK(c, hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, threads, 0));
+    HIPCHK(c, hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, threads_per_block(c->W), 0));
     HIPCHK(c, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->cfg.device));
-    const int G = groups_per_block(c->W);
-    const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((count + G - 1) / G,
-                                                                           (uint64_t)cus * std::max(per_cu, 1)));
-    HIPCHK(c, hipMemsetAsync(c->d_counters, 0, sizeof(unsigned long long) * NCOUNTERS_ALLOC, c->stream));
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-    void* params[] = {&a};
-    HIPCHK(c, hipModuleLaunchKernel(fn, grid, 1, 1, (unsigned)threads, 1, 1, 0, c->stream, params, nullptr));
-    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-    unsigned long long host[NCOUNTERS_ALLOC];
-    HIPCHK(c, hipMemcpyAsync(host, c->d_counters, sizeof(host), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    // a fused module compiled with -DPSG_PHASE_TIMERS=1 (formula.compile_native(defines=...)) run
-    // through a profiling build of the library
-    if (PSG_PHASE_TIMERS && std::getenv("PSG_PHASE_TIMERS")) print_timers(host);
-    float ms = 0.f;
-    HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    if (out) {
-      out->instances = (int64_t)count;
-      out->process_rounds = (int64_t)count * c->cfg.n * c->cfg.rounds;
-      out->active_process_rounds = (int64_t)host[C_ACTIVE];
-      out->live_instance_rounds = (int64_t)host[C_LIVE];
-      for (int i = 0; i < PSG_MAX_CHECKS; ++i) out->fail_count[i] = (int64_t)host[C_FAIL + i];
-      out->decided_processes = (int64_t)host[C_DECIDED];
-      out->digest = (int64_t)host[C_DIGEST];
-      for (int i = 0; i < R + 2; ++i) out->term_hist[i] = (int64_t)host[C_HIST + i];
-      out->kernel_ns = (int64_t)((double)ms * 1e6);
-    }
-    c->last_count = count;
-    if (per_inst)
-      HIPCHK(c, hipMemcpy(per_inst, c->d_inst, sizeof(psg_instance_summary) * count, hipMemcpyDeviceToHost));
-    return PSG_OK;
+    return run_whole_batch(c, inst_begin, count, out, per_inst, fn, (uint64_t)cus * std::max(per_cu, 1));
   }
   // trace chunk: <= PSG_SPEC_TRACE_MB (default 2048) MiB of [R+1][fields][n] int32 rows
   uint64_t budget = 2048ull << 20;
@@ -973,17 +959,11 @@ int psg_run_batch_spec(psg_ctx* c, uint64_t inst_begin, uint64_t count, const ps
   }
   const uint64_t per_inst_bytes = (uint64_t)(R + 1) * PSG_NFIELDS * (uint64_t)n * sizeof(int32_t);
   const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(count, budget / per_inst_bytes));
-  if (chunk > c->trace_cap) {
-    if (c->d_trace) (void)hipFree(c->d_trace);
-    c->d_trace = nullptr;
-    c->trace_cap = 0;
-    HIPCHK(c, hipMalloc(&c->d_trace, per_inst_bytes * chunk));
-    c->trace_cap = chunk;
-  }
-  if (!c->d_vm_counters) HIPCHK(c, hipMalloc(&c->d_vm_counters, sizeof(unsigned long long) * NCOUNTERS));
-  if (!c->d_vm_err) HIPCHK(c, hipMalloc(&c->d_vm_err, sizeof(int32_t)));
+  HIPCHK(c, c->d_trace.grow(per_inst_bytes / sizeof(int32_t) * chunk));
+  HIPCHK(c, c->d_vm_counters.grow(NCOUNTERS));
+  HIPCHK(c, c->d_vm_err.grow(1));
   HIPCHK(c, hipMemsetAsync(c->d_vm_err, 0, sizeof(int32_t), c->stream));
-  const bool staged = c->staged && c->staged_begin == inst_begin && c->staged_count == count;
+  const bool staged = is_staged(c, inst_begin, count);
   const uint32_t fields = prog_fields(prog);
   psg_summary acc;
   std::memset(&acc, 0, sizeof(acc));
@@ -1023,9 +1003,9 @@ int psg_run_batch_spec(psg_ctx* c, uint64_t inst_begin, uint64_t count, const ps
     if (native) {
       const int G = groups_per_block(c->W);
       const unsigned grid = (unsigned)std::min<uint64_t>((m_cnt + G - 1) / G, (uint64_t)vm_grid);
-      const unsigned threads = c->W == 1 ? 256u : 64u * (unsigned)c->W;
       void* params[] = {&v};
-      HIPCHK(c, hipModuleLaunchKernel(c->native_fn, grid, 1, 1, threads, 1, 1, 0, c->stream, params, nullptr));
+      HIPCHK(c, hipModuleLaunchKernel(c->native_fn, grid, 1, 1, (unsigned)threads_per_block(c->W), 1, 1, 0, c->stream,
+                                      params, nullptr));
     } else {
       HIPCHK(c, launch_spec_vm(v, (int)std::min<uint64_t>(m_cnt, (uint64_t)vm_grid), c->stream));
     }
@@ -1035,15 +1015,9 @@ int psg_run_batch_spec(psg_ctx* c, uint64_t inst_begin, uint64_t count, const ps
     HIPCHK(c, hipStreamSynchronize(c->stream));
     float ms = 0.f;
     HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    acc.instances += part.instances;
-    acc.process_rounds += part.process_rounds;
-    acc.active_process_rounds += part.active_process_rounds;
-    acc.live_instance_rounds += part.live_instance_rounds;
-    acc.decided_processes += part.decided_processes;
-    acc.digest = (int64_t)((uint64_t)acc.digest + (uint64_t)part.digest);
-    acc.kernel_ns += part.kernel_ns + (int64_t)((double)ms * 1e6);
-    for (int i = 0; i < PSG_MAX_CHECKS; ++i) acc.fail_count[i] += (int64_t)host[C_FAIL + i];
-    for (int i = 0; i < R + 2; ++i) acc.term_hist[i] += (int64_t)host[C_HIST + i];
+    fill_summary(part, host, R, true);  // the Spec's slots and Termination, not the built-in checks'
+    summary_add(acc, part);
+    acc.kernel_ns += part.kernel_ns + (int64_t)((double)ms * 1e6);  // the chunks ran one after the other
   }
   int32_t verr = 0;
   HIPCHK(c, hipMemcpy(&verr, c->d_vm_err, sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -1062,18 +1036,10 @@ int psg_run_batch_spec(psg_ctx* c, uint64_t inst_begin, uint64_t count, const ps
 int psg_copy_decisions_f64(psg_ctx* c, double* decision, int32_t* decision_round) {
   if (!c) return PSG_EINVAL;
   if (c->cfg.alg != PSG_ALG_EPSILON) return fail(c, PSG_EINVAL, "Double decisions are for EpsilonConsensus only");
-  if (!c->subs.empty()) {
-    const uint64_t n = (uint64_t)c->cfg.n, nd = c->subs.size();
-    for (size_t d = 0; d < nd; ++d) {
-      uint64_t off, m;
-      split(c->last_count, nd, d, off, m);
-      if (!m) continue;
-      const int rc = psg_copy_decisions_f64(c->subs[d], decision ? decision + off * n : nullptr,
-                                            decision_round ? decision_round + off * n : nullptr);
-      if (rc) return fail(c, rc, "device " + std::to_string(c->cfg.devices[d]) + ": " + c->subs[d]->err);
-    }
-    return PSG_OK;
-  }
+  if (!c->subs.empty())
+    return each_last_slice(c, [&](psg_ctx* s, uint64_t at) {
+      return psg_copy_decisions_f64(s, decision ? decision + at : nullptr, decision_round ? decision_round + at : nullptr);
+    });
   HIPCHK(c, hipSetDevice(c->cfg.device));
   const uint64_t cells = c->last_count * (uint64_t)c->cfg.n;
   if (decision) HIPCHK(c, hipMemcpy(decision, c->d_dec_f64, sizeof(double) * cells, hipMemcpyDeviceToHost));
@@ -1174,21 +1140,9 @@ static int fetch_impl(psg_ctx* c, const uint64_t* ids, size_t k, psg_instance_su
   if (k == 0) return PSG_OK;
   if (k > c->cap) return fail(c, PSG_ERANGE, "fetch count exceeds batch_capacity");
   HIPCHK(c, hipSetDevice(c->cfg.device));
-  if (k > c->fetch_cap) {
-    if (c->d_ids) (void)hipFree(c->d_ids);
-    if (c->d_rec) (void)hipFree(c->d_rec);
-    c->d_ids = nullptr;
-    c->d_rec = nullptr;
-    c->fetch_cap = 0;
-    HIPCHK(c, hipMalloc(&c->d_ids, sizeof(uint64_t) * k));
-    HIPCHK(c, hipMalloc(&c->d_rec, sizeof(psg_process_record) * k * (uint64_t)c->cfg.n));
-    if (c->cfg.alg == PSG_ALG_EPSILON) {
-      if (c->d_rec_f64) (void)hipFree(c->d_rec_f64);
-      c->d_rec_f64 = nullptr;
-      HIPCHK(c, hipMalloc(&c->d_rec_f64, sizeof(double) * 2 * k * (uint64_t)c->cfg.n));
-    }
-    c->fetch_cap = k;
-  }
+  HIPCHK(c, c->d_ids.grow(k));
+  HIPCHK(c, c->d_rec.grow(k * (uint64_t)c->cfg.n));
+  if (c->cfg.alg == PSG_ALG_EPSILON) HIPCHK(c, c->d_rec_f64.grow(2 * k * (uint64_t)c->cfg.n));
   bool in_staged = c->staged && !force_seeded;
   for (size_t j = 0; j < k; ++j) {
     if (int rc = check_sched_range(c, ids[j], 1)) return rc;
@@ -1229,45 +1183,44 @@ static int fetch_impl(psg_ctx* c, const uint64_t* ids, size_t k, psg_instance_su
   return PSG_OK;
 }
 
+// uint64 words of one instance's HO sets, ho[k][p][W]
+static uint64_t sched_words(const psg_ctx* c) { return (uint64_t)c->cfg.rounds * (uint64_t)c->cfg.n * (uint64_t)c->W; }
+
+// Room for the explicit schedule of `count` instances (psg_load_schedule, populations). A regrow
+// drops the loaded schedule.
+static int sched_buffers(psg_ctx* c, uint64_t count) {
+  const uint64_t words = count * sched_words(c), crashes = count * (uint64_t)c->cfg.n;
+  if (words > c->d_ho.cap || crashes > c->d_crash.cap) c->ho_loaded = false;
+  HIPCHK(c, c->d_ho.grow(words));
+  HIPCHK(c, c->d_crash.grow(crashes));
+  return PSG_OK;
+}
+
 int psg_load_schedule(psg_ctx* c, uint64_t inst_begin, uint64_t count, const uint64_t* ho,
                       const int32_t* crash_round) {
   if (!c) return PSG_EINVAL;
   if (!ho && count) return fail(c, PSG_EINVAL, "null schedule");
   if (count > c->cap) return fail(c, PSG_ERANGE, "inst_count exceeds batch_capacity");
+  const uint64_t n = (uint64_t)c->cfg.n, per = sched_words(c);
   if (!c->subs.empty()) {
-    const uint64_t per = (uint64_t)c->cfg.rounds * (uint64_t)c->cfg.n * (uint64_t)c->W, nd = c->subs.size();
+    const uint64_t nd = c->subs.size();
     const int rc = par_subs(c, [&](size_t d) {
       uint64_t off, m;
       split(count, nd, d, off, m);
       return psg_load_schedule(c->subs[d], inst_begin + off, m, ho ? ho + off * per : nullptr,
-                               crash_round ? crash_round + off * (uint64_t)c->cfg.n : nullptr);
+                               crash_round ? crash_round + off * n : nullptr);
     });
     if (rc) return rc;
-    c->ho_loaded = true;
-    c->ho_has_crash = crash_round != nullptr;
-    c->ho_begin = inst_begin;
-    c->ho_count = count;
-    return PSG_OK;
-  }
-  HIPCHK(c, hipSetDevice(c->cfg.device));
-  const uint64_t n = (uint64_t)c->cfg.n, R = (uint64_t)c->cfg.rounds, W = (uint64_t)c->W;
-  if (count > c->ho_cap) {
-    if (c->d_ho) (void)hipFree(c->d_ho);
-    if (c->d_crash) (void)hipFree(c->d_crash);
-    c->d_ho = nullptr;
-    c->d_crash = nullptr;
-    c->ho_cap = 0;
-    c->ho_loaded = false;
-    HIPCHK(c, hipMalloc(&c->d_ho, sizeof(uint64_t) * count * R * n * W));
-    HIPCHK(c, hipMalloc(&c->d_crash, sizeof(int32_t) * count * n));
-    c->ho_cap = count;
-  }
-  if (count) {
-    HIPCHK(c, hipMemcpyAsync(c->d_ho, ho, sizeof(uint64_t) * count * R * n * W, hipMemcpyHostToDevice, c->stream));
-    if (crash_round)
-      HIPCHK(c, hipMemcpyAsync(c->d_crash, crash_round, sizeof(int32_t) * count * n, hipMemcpyHostToDevice,
-                               c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+  } else {
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    if (int rc = sched_buffers(c, count)) return rc;
+    if (count) {
+      HIPCHK(c, hipMemcpyAsync(c->d_ho, ho, sizeof(uint64_t) * count * per, hipMemcpyHostToDevice, c->stream));
+      if (crash_round)
+        HIPCHK(c, hipMemcpyAsync(c->d_crash, crash_round, sizeof(int32_t) * count * n, hipMemcpyHostToDevice,
+                                 c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
   }
   c->ho_loaded = true;
   c->ho_has_crash = crash_round != nullptr;
@@ -1289,25 +1242,23 @@ int psg_materialize_schedule(psg_ctx* c, uint64_t inst_begin, uint64_t count, ui
   if (!c) return PSG_EINVAL;
   if (!ho && count) return fail(c, PSG_EINVAL, "null output");
   if (count == 0) return PSG_OK;
+  const uint64_t n = (uint64_t)c->cfg.n, per = sched_words(c);
   if (!c->subs.empty()) {
-    const uint64_t per = (uint64_t)c->cfg.rounds * (uint64_t)c->cfg.n * (uint64_t)c->W, nd = c->subs.size();
+    const uint64_t nd = c->subs.size();
     return par_subs(c, [&](size_t d) {
       uint64_t off, m;
       split(count, nd, d, off, m);
       return m ? psg_materialize_schedule(c->subs[d], inst_begin + off, m, ho + off * per,
-                                          crash_round ? crash_round + off * (uint64_t)c->cfg.n : nullptr)
+                                          crash_round ? crash_round + off * n : nullptr)
                : PSG_OK;
     });
   }
   HIPCHK(c, hipSetDevice(c->cfg.device));
-  const uint64_t n = (uint64_t)c->cfg.n, R = (uint64_t)c->cfg.rounds, W = (uint64_t)c->W;
-  const uint64_t per = R * n * W * sizeof(uint64_t);
-  const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(count, (256ull << 20) / per));
-  uint64_t* d_out = nullptr;
-  int32_t* d_cr = nullptr;
-  hipError_t e = hipMalloc(&d_out, per * chunk);
-  if (e == hipSuccess) e = hipMalloc(&d_cr, sizeof(int32_t) * n * chunk);
-  int rc = PSG_OK;
+  const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(count, (256ull << 20) / (per * sizeof(uint64_t))));
+  DevBuf<uint64_t> d_out;
+  DevBuf<int32_t> d_cr;
+  hipError_t e = d_out.grow(per * chunk);
+  if (e == hipSuccess) e = d_cr.grow(n * chunk);
   KArgs a = make_args(c);
   a.ho_in = nullptr;  // always the seeded generator
   a.crash_in = nullptr;
@@ -1318,47 +1269,27 @@ int psg_materialize_schedule(psg_ctx* c, uint64_t inst_begin, uint64_t count, ui
     a.count = m;
     const int grid = (int)std::min<uint64_t>((m + G - 1) / G, (uint64_t)c->grid_max);
     e = launch_schedule(a, c->W, grid, d_out, d_cr, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(ho + off * R * n * W, d_out, per * m, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(ho + off * per, d_out, sizeof(uint64_t) * per * m, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess && crash_round)
       e = hipMemcpyAsync(crash_round + off * n, d_cr, sizeof(int32_t) * n * m, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   }
-  if (e != hipSuccess) rc = hip_fail(c, e, "psg_materialize_schedule");
-  if (d_out) (void)hipFree(d_out);
-  if (d_cr) (void)hipFree(d_cr);
-  return rc;
+  return e == hipSuccess ? PSG_OK : hip_fail(c, e, "psg_materialize_schedule");
 }
 
 // ---------------------------------------------------------------- search populations
+// Instances the population's second buffers hold (d_op is grown with d_parent).
+static uint64_t pop_capacity(const psg_ctx* c) { return std::min(c->d_ho2.cap / sched_words(c), c->d_parent.cap); }
+
 static int pop_buffers(psg_ctx* c, uint64_t count) {
-  const uint64_t n = (uint64_t)c->cfg.n, R = (uint64_t)c->cfg.rounds, W = (uint64_t)c->W;
-  if (count > c->ho_cap) {  // the loaded-schedule buffers (psg_load_schedule's)
-    if (c->d_ho) (void)hipFree(c->d_ho);
-    if (c->d_crash) (void)hipFree(c->d_crash);
-    c->d_ho = nullptr;
-    c->d_crash = nullptr;
-    c->ho_cap = 0;
-    c->ho_loaded = false;
-    HIPCHK(c, hipMalloc(&c->d_ho, sizeof(uint64_t) * count * R * n * W));
-    HIPCHK(c, hipMalloc(&c->d_crash, sizeof(int32_t) * count * n));
-    c->ho_cap = count;
-  }
-  if (count > c->pop_cap) {
-    if (c->d_ho2) (void)hipFree(c->d_ho2);
-    if (c->d_init2) (void)hipFree(c->d_init2);
-    if (c->d_parent) (void)hipFree(c->d_parent);
-    if (c->d_op) (void)hipFree(c->d_op);
-    c->d_ho2 = nullptr;
-    c->d_init2 = nullptr;
-    c->d_parent = nullptr;
-    c->d_op = nullptr;
-    c->pop_cap = 0;
-    const uint64_t cap = std::max(count, c->ho_cap);
-    HIPCHK(c, hipMalloc(&c->d_ho2, sizeof(uint64_t) * cap * R * n * W));
-    HIPCHK(c, hipMalloc(&c->d_init2, sizeof(int32_t) * c->cap * n));
-    HIPCHK(c, hipMalloc(&c->d_parent, sizeof(uint32_t) * cap));
-    HIPCHK(c, hipMalloc(&c->d_op, cap));
-    c->pop_cap = cap;
+  if (int rc = sched_buffers(c, count)) return rc;  // the loaded-schedule buffers (psg_load_schedule's)
+  if (count > pop_capacity(c)) {
+    const uint64_t cap = std::max(count, c->d_ho.cap / sched_words(c));  // at least the instances d_ho holds
+    HIPCHK(c, c->d_ho2.grow(cap * sched_words(c)));
+    HIPCHK(c, c->d_init2.grow(c->cap * (uint64_t)c->cfg.n));
+    HIPCHK(c, c->d_parent.grow(cap));
+    HIPCHK(c, c->d_op.grow(cap));
   }
   return PSG_OK;
 }
@@ -1406,9 +1337,7 @@ int psg_population_fresh(psg_ctx* c, uint64_t inst_begin, uint64_t count, const 
   c->ho_has_crash = false;
   c->ho_begin = inst_begin;
   c->ho_count = count;
-  c->staged = true;
-  c->staged_begin = inst_begin;
-  c->staged_count = count;
+  set_staged(c, inst_begin, count, false);
   return PSG_OK;
 }
 
@@ -1416,8 +1345,7 @@ int psg_population_next(psg_ctx* c, const uint32_t* parent, const uint8_t* op, c
   if (!c) return PSG_EINVAL;
   if (!c->subs.empty()) return fail(c, PSG_EINVAL, "device-resident populations need a single-device context");
   if (int rc = pop_check(c, p)) return rc;
-  if (!(c->ho_loaded && c->staged && c->staged_begin == c->ho_begin && c->staged_count == c->ho_count) ||
-      c->pop_cap < c->ho_count)
+  if (!(c->ho_loaded && is_staged(c, c->ho_begin, c->ho_count)) || pop_capacity(c) < c->ho_count)
     return fail(c, PSG_EINVAL, "no population loaded (psg_population_fresh first)");
   const uint64_t count = c->ho_count;
   if (count && (!parent || !op)) return fail(c, PSG_EINVAL, "null parent / op");
@@ -1437,10 +1365,8 @@ int psg_population_next(psg_ctx* c, const uint32_t* parent, const uint8_t* op, c
   a.op = c->d_op;
   HIPCHK(c, launch_population(a, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  std::swap(c->d_ho, c->d_ho2);  // the new generation is the loaded schedule / staged inputs
-  std::swap(c->d_init, c->d_init2);
-  std::swap(c->ho_cap, c->pop_cap);
-  c->pop_cap = std::min(c->pop_cap, c->ho_cap);
+  std::swap(c->d_ho, c->d_ho2);  // the new generation is the loaded schedule / staged inputs; the
+  std::swap(c->d_init, c->d_init2);  // capacities go with the buffers
   return PSG_OK;
 }
 
@@ -1471,27 +1397,7 @@ void psg_destroy(psg_ctx* c) {
   }
   (void)hipSetDevice(c->cfg.device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  if (c->d_init) (void)hipFree(c->d_init);
-  if (c->d_dec) (void)hipFree(c->d_dec);
-  if (c->d_dround) (void)hipFree(c->d_dround);
-  if (c->d_inst) (void)hipFree(c->d_inst);
-  if (c->d_counters) (void)hipFree(c->d_counters);
-  if (c->d_hand) (void)hipFree(c->d_hand);
-  if (c->d_ids) (void)hipFree(c->d_ids);
-  if (c->d_rec) (void)hipFree(c->d_rec);
-  if (c->d_init_f64) (void)hipFree(c->d_init_f64);
-  if (c->d_dec_f64) (void)hipFree(c->d_dec_f64);
-  if (c->d_rec_f64) (void)hipFree(c->d_rec_f64);
-  if (c->d_trace) (void)hipFree(c->d_trace);
-  if (c->d_vm_counters) (void)hipFree(c->d_vm_counters);
-  if (c->d_vm_err) (void)hipFree(c->d_vm_err);
-  if (c->d_prog) (void)hipFree(c->d_prog);
-  if (c->d_ho) (void)hipFree(c->d_ho);
-  if (c->d_crash) (void)hipFree(c->d_crash);
-  if (c->d_ho2) (void)hipFree(c->d_ho2);
-  if (c->d_init2) (void)hipFree(c->d_init2);
-  if (c->d_parent) (void)hipFree(c->d_parent);
-  if (c->d_op) (void)hipFree(c->d_op);
+  static_cast<psg_buffers&>(*c) = psg_buffers();  // frees every device buffer, before the stream goes
   if (c->module) (void)hipModuleUnload(c->module);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);

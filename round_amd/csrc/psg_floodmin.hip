@@ -445,23 +445,11 @@ static hipError_t launch_w(const KArgs& a, int grid, hipStream_t s) {
 }
 
 hipError_t launch_floodmin(const KArgs& a, int W, int grid, hipStream_t s) {
-  switch (W) {
-    case 1: return launch_w<1>(a, grid, s);
-    case 2: return launch_w<2>(a, grid, s);
-    case 3: return launch_w<3>(a, grid, s);
-    case 4: return launch_w<4>(a, grid, s);
-  }
-  return hipErrorInvalidValue;
+  return with_w(W, hipErrorInvalidValue, [&](auto w) { return launch_w<w()>(a, grid, s); });
 }
 
 const void* floodmin_kernel_ptr(int W) {
-  switch (W) {
-    case 1: return (const void*)floodmin_kernel<1, false>;
-    case 2: return (const void*)floodmin_kernel<2, false>;
-    case 3: return (const void*)floodmin_kernel<3, false>;
-    case 4: return (const void*)floodmin_kernel<4, false>;
-  }
-  return nullptr;
+  return with_w(W, (const void*)nullptr, [](auto w) { return (const void*)floodmin_kernel<w(), false>; });
 }
 
 #endif  // PSG_FUSED_MODULE

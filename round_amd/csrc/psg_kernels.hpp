@@ -3,10 +3,25 @@
 #ifndef __HIPCC_RTC__  // (a hiprtc build of a fused Spec module has no host launchers)
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 namespace psg {
 struct KArgs;
 struct VmArgs;
 struct PopArgs;
+
+// Runtime W (mask words, 1..4) -> compile-time constant: f(std::integral_constant<int, W>) for a
+// generic callable f, `bad` outside that range.
+template <class R, class F>
+R with_w(int W, R bad, F&& f) {
+  switch (W) {
+    case 1: return f(std::integral_constant<int, 1>());
+    case 2: return f(std::integral_constant<int, 2>());
+    case 3: return f(std::integral_constant<int, 3>());
+    case 4: return f(std::integral_constant<int, 4>());
+  }
+  return bad;
+}
 
 hipError_t launch_otr(const KArgs& a, int W, int grid, hipStream_t s);
 hipError_t launch_lv(const KArgs& a, int W, int grid, hipStream_t s);

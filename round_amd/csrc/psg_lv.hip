@@ -438,23 +438,11 @@ static hipError_t launch_w(const KArgs& a, int grid, hipStream_t s) {
 }
 
 hipError_t launch_lv(const KArgs& a, int W, int grid, hipStream_t s) {
-  switch (W) {
-    case 1: return launch_w<1>(a, grid, s);
-    case 2: return launch_w<2>(a, grid, s);
-    case 3: return launch_w<3>(a, grid, s);
-    case 4: return launch_w<4>(a, grid, s);
-  }
-  return hipErrorInvalidValue;
+  return with_w(W, hipErrorInvalidValue, [&](auto w) { return launch_w<w()>(a, grid, s); });
 }
 
 const void* lv_kernel_ptr(int W) {
-  switch (W) {
-    case 1: return (const void*)lv_kernel<1, false, NoHook, false>;
-    case 2: return (const void*)lv_kernel<2, false, NoHook, false>;
-    case 3: return (const void*)lv_kernel<3, false, NoHook, false>;
-    case 4: return (const void*)lv_kernel<4, false, NoHook, false>;
-  }
-  return nullptr;
+  return with_w(W, (const void*)nullptr, [](auto w) { return (const void*)lv_kernel<w(), false, NoHook, false>; });
 }
 
 #endif  // PSG_FUSED_MODULE

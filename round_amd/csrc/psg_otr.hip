@@ -330,24 +330,12 @@ static hipError_t launch_w(const KArgs& a, int grid, hipStream_t s) {
 
 template <bool V2>
 static hipError_t launch_v(const KArgs& a, int W, int grid, hipStream_t s) {
-  switch (W) {
-    case 1: return launch_w<1, V2>(a, grid, s);
-    case 2: return launch_w<2, V2>(a, grid, s);
-    case 3: return launch_w<3, V2>(a, grid, s);
-    case 4: return launch_w<4, V2>(a, grid, s);
-  }
-  return hipErrorInvalidValue;
+  return with_w(W, hipErrorInvalidValue, [&](auto w) { return launch_w<w(), V2>(a, grid, s); });
 }
 
 template <bool V2>
 static const void* ptr_v(int W) {
-  switch (W) {
-    case 1: return (const void*)otr_kernel<1, V2, false, NoHook, false>;
-    case 2: return (const void*)otr_kernel<2, V2, false, NoHook, false>;
-    case 3: return (const void*)otr_kernel<3, V2, false, NoHook, false>;
-    case 4: return (const void*)otr_kernel<4, V2, false, NoHook, false>;
-  }
-  return nullptr;
+  return with_w(W, (const void*)nullptr, [](auto w) { return (const void*)otr_kernel<w(), V2, false, NoHook, false>; });
 }
 
 hipError_t launch_otr(const KArgs& a, int W, int grid, hipStream_t s) { return launch_v<false>(a, W, grid, s); }

@@ -48,14 +48,10 @@ __global__ void __launch_bounds__(Geometry<W>::kThreads) schedule_kernel(KArgs a
 }
 
 hipError_t launch_schedule(const KArgs& a, int W, int grid, uint64_t* ho_out, int32_t* crash_out, hipStream_t s) {
-  switch (W) {
-    case 1: hipLaunchKernelGGL(schedule_kernel<1>, dim3(grid), dim3(Geometry<1>::kThreads), 0, s, a, ho_out, crash_out); break;
-    case 2: hipLaunchKernelGGL(schedule_kernel<2>, dim3(grid), dim3(Geometry<2>::kThreads), 0, s, a, ho_out, crash_out); break;
-    case 3: hipLaunchKernelGGL(schedule_kernel<3>, dim3(grid), dim3(Geometry<3>::kThreads), 0, s, a, ho_out, crash_out); break;
-    case 4: hipLaunchKernelGGL(schedule_kernel<4>, dim3(grid), dim3(Geometry<4>::kThreads), 0, s, a, ho_out, crash_out); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_w(W, hipErrorInvalidValue, [&](auto w) {
+    hipLaunchKernelGGL(schedule_kernel<w()>, dim3(grid), dim3(Geometry<w()>::kThreads), 0, s, a, ho_out, crash_out);
+    return hipGetLastError();
+  });
 }
 
 }  // namespace psg

@@ -319,6 +319,52 @@ def test_population_argument_errors():
             g._ctx.population_fresh(0, 8, _pop_params())
 
 
+def test_buffers_regrow_inside_a_live_context():
+    """Every growable device buffer grows inside one live context (fetch ids / records, the
+    explicit schedule, the Spec program and its trace, the population generations), and what the
+    context computes after each regrow equals what it computed before, or what a fresh context gives."""
+    from round_amd import formula
+    n, R, cap = 8, 4, 64
+
+    def rows(pi):
+        return [(s.digest, tuple(s.first_fail), s.term_round) for s in pi]
+
+    def population(ctx, P, nxt):
+        ctx.population_fresh(0, P, _pop_params())
+        if nxt:
+            ctx.population_next(np.arange(P, dtype=np.uint32)[::-1].copy(), (np.arange(P) % 3).astype(np.uint8),
+                                _pop_params(gen=1))
+        return ctx.population_read(np.arange(P))
+
+    with psync.GpuRound(psync.OTR(), n, R, seed=7, batch_capacity=cap) as g:
+        want = rows(g.run(0, cap, per_instance=True).per_instance)
+        for ids in ([5, 60], list(range(3, 43))):  # 2 ids, then 40
+            sums, _ = g.fetch(ids)
+            assert rows(sums) == [want[i] for i in ids]
+        for I in (4, 32):  # a materialized schedule replays the seeded run of its range
+            ho, crash = g.materialize_schedule(0, I)
+            g.load_schedule(0, I, ho, crash)
+            assert rows(g.run(0, I, per_instance=True).per_instance) == want[:I]
+        g.clear_schedule()
+        # the Spec VM: the properties alone over 8 instances, then the whole OTR Spec over 64
+        short = formula.Spec(properties=formula.otr_spec().properties)
+        for I, spec, first in ((8, short, 4), (cap, formula.otr_spec(), 0)):
+            built = g.run(0, I).summary
+            res = g.run_spec(0, I, spec)
+            k = len(res.slot_names)
+            assert res.slot_names == psync.OTR().check_names[first:first + k]
+            assert list(res.summary.fail_count)[:k] == list(built.fail_count)[first:first + k]
+            assert list(res.summary.term_hist)[:R + 2] == list(built.term_hist)[:R + 2]
+        for P, nxt in ((8, False), (cap, False), (cap, True)):  # 8 rows, then 64, then the next generation
+            got = population(g._ctx, P, nxt)
+            with psync.GpuRound(psync.OTR(), n, R, seed=7, batch_capacity=cap) as f:
+                ref = population(f._ctx, P, nxt)
+                if nxt:  # and the kernels run the swapped-in generation
+                    assert rows(f.run(0, P, per_instance=True).per_instance) == rows(
+                        g.run(0, P, per_instance=True).per_instance)
+            assert all((a == b).all() for a, b in zip(got, ref)), (P, nxt)
+
+
 def test_device_and_host_search_paths_agree_on_outcome():
     """The device-population search and the host one both find the OTR mutant."""
     for dp in (True, False):

@@ -56,6 +56,13 @@ def _c_entries():
     return out
 
 
+def _built_so():
+    """The shim's test build; made here when build() has not left it in the tree."""
+    if not os.path.exists(SO):
+        subprocess.check_call(["make", "-s", "-C", os.path.dirname(SO)])
+    return SO
+
+
 def test_every_native_method_has_a_matching_entry_point():
     """JNI name mangling of `object GpuRoundNative` (GpuRoundNative$ -> _00024) and the
     parameter / return types of each @native def."""
@@ -65,7 +72,7 @@ def test_every_native_method_has_a_matching_entry_point():
         cparams, cret = c[name]
         assert [SCALA_TO_JNI[p] for p in params] == cparams, name
         assert SCALA_TO_JNI[ret] == cret, name
-    nm = subprocess.check_output(["nm", "-D", "--defined-only", SO]).decode()
+    nm = subprocess.check_output(["nm", "-D", "--defined-only", _built_so()]).decode()
     for name in scala:
         assert f"Java_psync_gpu_GpuRoundNative_00024_{name}" in nm
 
@@ -113,8 +120,7 @@ class Shim:
 
 @pytest.fixture(scope="module")
 def shim():
-    if not os.path.exists(SO):
-        subprocess.check_call(["make", "-s", "-C", os.path.dirname(SO)])
+    _built_so()
     return Shim()
 
 
