@@ -354,6 +354,15 @@ PSG_DEV uint32_t nz01(uint32_t x) {
   return x != 0;
 #endif
 }
+// The same for a wave-uniform word: an opaque copy in a scalar register (no instruction), so
+// that 0/1 facts formed from it stay 32-bit scalar integers.
+PSG_DEV uint32_t opaque_uniform(uint32_t x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  x = (uint32_t)__builtin_amdgcn_readfirstlane((int)x);  // no instruction where x is already scalar
+  asm("" : "+s"(x));
+#endif
+  return x;
+}
 PSG_DEV uint32_t ne01(int32_t a, int32_t b) { return nz01((uint32_t)(a ^ b)); }
 PSG_DEV uint32_t eq01(int32_t a, int32_t b) { return 1u - nz01((uint32_t)(a ^ b)); }
 PSG_DEV uint32_t gt01(int32_t a, int32_t b) { return (uint32_t)(((int64_t)b - (int64_t)a) >> 63) & 1u; }  // a > b
@@ -1162,6 +1171,18 @@ struct Checks {
     // past PSG_MAX_CHECKS take the all-zero mask instead, one AND + compare per check point)
     const uint32_t mine = lane <= PSG_MAX_CHECKS ? 1u << lane : 0u;
     const int32_t at = (bits & mine) ? c : (int32_t)PSG_NEVER;
+    ffv = at < ffv ? at : ffv;
+  }
+  // Check point c where every lane's result is a threshold test of one uniform count: the lane
+  // records iff cnt <= T, T its own threshold (-1: never, for cnt >= 0; INT32_MAX: always). One
+  // compare, one select, one min per lane, and no scalar fail word to form and test.
+  PSG_DEV void record_le(int32_t cnt, int32_t T, int c) {
+    int32_t at = cnt <= T ? c : (int32_t)PSG_NEVER;
+#if defined(__HIP_DEVICE_COMPILE__)
+    // opaque copy: keeps the compiler from merging this select with record()'s in a caller's
+    // other arm, through a lane-mask phi formed with three scalar instructions
+    asm("" : "+v"(at));
+#endif
     ffv = at < ffv ? at : ffv;
   }
   // slot `lane` (< PSG_MAX_CHECKS) failed at some check point

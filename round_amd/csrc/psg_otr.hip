@@ -21,6 +21,20 @@ struct OtrLds {
   int32_t ds[W > 1 ? 64 * W : 1];
 };
 
+// Per-lane thresholds of a check point in the settled state (otr_check_settled, W == 1), where a
+// lane records iff the vote count cnt <= its threshold (Checks::record_le): lane 1 (Invariant0)
+// 2n/3, for OTR2 never (its Invariant0 holds by term); lane 2 (Invariant1) n - 1; lane
+// PSG_MAX_CHECKS (Termination) always; every other lane never (-1 < 0 <= cnt). A function of n
+// and the lane alone: formed once per kernel.
+template <bool V2>
+PSG_DEV int32_t otr_check_thresholds(int n, int lane) {
+  int32_t t = -1;
+  if (!V2 && lane == 1) t = (2 * n) / 3;
+  if (lane == 2) t = n - 1;
+  if (lane == PSG_MAX_CHECKS) t = INT32_MAX;
+  return t;
+}
+
 // Spec check at check point c (spec r = c). Slots: 0 Safety (some invariant
 // holds), 1..3 invariants, 4 Agreement, 5 Validity, 6 Integrity, 7 Irrevocability.
 // Every formula is evaluated from scratch at every check point. The universally
@@ -37,40 +51,15 @@ struct OtrLds {
 // slower, profiles/s2_ab/ab5.log: the chain's latency; a compare + ballot has none.)
 // V.exists(v => |{i : i.x == v}| > 2n/3 && all decisions == v): with decisions only
 // v = d0 can qualify; without, v must be a strict majority (Boyer-Moore candidate).
-template <int W, bool V2, bool FROZEN = false>
-// od / ox: "decision / x maybe not initial" (X0Set::maybe_out01_2 of the current values), probed
-// by the caller when the values change (round 0 and executed updates) instead of at every check
-// point: the memoized probe of the fused lowering (DESIGN §5); every formula is still evaluated.
-// FROZEN: a check point of the frozen tail, where the pre-round state is the current one, so the
-// Irrevocability witness old.decided && !(decided && old.decision == decision) is 0 by algebra.
-PSG_DEV void otr_check(Grp<W>& g, OtrLds<W>& L, const X0Set<W>& X0, Checks& ck, int c, bool has_old, int n,
-                       const Mask<W>& full, int32_t x, uint32_t dec01, int32_t decision, uint32_t old01,
-                       int32_t old_decision, uint32_t valid01, uint32_t od, uint32_t ox) {
+// otr_check (below) is a check point: otr_check_settled, else otr_check_general.
+
+// The check outside the settled state (arguments as otr_check's; irr01 is the per-process
+// Irrevocability witness bit).
+template <int W, bool V2>
+PSG_DEV void otr_check_general(Grp<W>& g, OtrLds<W>& L, const X0Set<W>& X0, Checks& ck, int c, bool has_old, int n,
+                               const Mask<W>& full, int32_t x, uint32_t dec01, int32_t decision, uint32_t old01,
+                               int32_t old_decision, uint32_t valid01, uint32_t od, uint32_t ox, uint32_t irr01) {
   const int sthr = (2 * n) / 3;  // 2*n/3 in the Spec (Otr.scala:101)
-  if constexpr (W > 1) {
-    L.ds[g.pid] = decision;
-    __syncthreads();
-  }
-  const uint32_t irr01 = (has_old && !FROZEN) ? old01 & (1u - (dec01 & eq01(old_decision, decision))) : 0u;
-  {
-    // Settled state first (every process decided, every decision equal to process 0's, no
-    // witness): one ballot of a per-process word, with process 0's decision as d0 (when all
-    // decided, process 0 is the first decider). Then keepInit, Validity, Agreement and
-    // Irrevocability hold, so Invariant2 (OTR: term && all decisions equal and initial;
-    // OTR2: all decisions equal), Safety and Integrity hold; Invariant0 reduces to e0
-    // (OTR2: term), Invariant1 to e1, with the vote count taken at v = d0. The same values
-    // as the general path below, in a few instructions (most check points of a run are in
-    // this state).
-    const int32_t p0 = g.bcast(decision, L.ds, 0);
-    uint32_t u = (1u - dec01) | od | ne01(decision, p0) | irr01;
-    if constexpr (!V2) u |= ox;  // keepInit (OTR only)
-    if (!g.any((u & valid01) != 0u)) {
-      const int cnt = mpopc(g.ballot(x == p0));  // (a compare and the valid-lane mask)
-      const uint32_t fb = (V2 ? 0u : fbit(cnt > sthr, 1)) | fbit(cnt == n, 2);
-      ck.record(fb, true, c, g.lane);
-      return;
-    }
-  }
   // dec01 and the witness word are 0 on lanes past n: ballots without the valid-lane mask
   const Mask<W> D = g.ballot_any(dec01 != 0u);
   const bool anyD = many(D);
@@ -82,18 +71,49 @@ PSG_DEV void otr_check(Grp<W>& g, OtrLds<W>& L, const X0Set<W>& X0, Checks& ck, 
   const Mask<W> Wm = g.ballot_any((wit & valid01) != 0u);
   const bool term = meq(D, full);
   const bool wany = many(Wm);
+  // the vote count's value: d0 once someone decided; before that OTR reads the count only as
+  // cnt == n (Invariant1; Invariant0 is keepInit alone with no decision), which holds iff every
+  // x equals process 0's — the majority candidate is needed only for OTR2's e0 (and W > 1)
+  auto vote_count = [&]() -> int {
+    const int32_t ref = anyD ? d0 : ((!V2 && W == 1) ? readlane32(x, 0) : majority_candidate<W>(g, x));
+    return mpopc(g.ballot((valid01 & eq01(x, ref)) != 0u));
+  };
+  // W == 1 counts before the two arms, which share it; W > 1 keeps the one general form below,
+  // with the count after the witness ballots (the no-witness arm costs it an occupancy step)
+  int cnt = 0;
+  if constexpr (W == 1) cnt = vote_count();
+  if (W == 1 && !wany) {
+    // No witness (the usual state before everyone has decided): keepInit, Validity, Agreement
+    // ("same") and Irrevocability hold, and the formulas of the exact arm below reduce to
+    // functions of anyD, term and cnt. OTR: Invariant0 = !anyD || cnt > 2n/3, Invariant1 =
+    // (cnt == n), Invariant2 = term, Safety their disjunction (cnt <= 2n/3 implies cnt < n);
+    // OTR2: Invariant0 = term || cnt > 2n/3, Invariant1 = (cnt == n), Invariant2 and Safety hold;
+    // Integrity holds in both. Every one is evaluated here, as 0/1 integers behind opaque copies:
+    // a uniform bool the compiler recognises is a 64-bit lane mask (opaque_uniform).
+    const uint32_t les = opaque_uniform((uint32_t)(cnt - sthr - 1));  // sign bit: cnt <= 2n/3
+    const uint32_t ne = opaque_uniform((uint32_t)(cnt - n)) >> 31;    // cnt != n (cnt <= n always)
+    uint32_t fb;
+    if constexpr (V2) {
+      const uint32_t t = opaque_uniform(term ? 1u : 0u);
+      fb = (t << PSG_MAX_CHECKS) | (((t ^ 1u) & (les >> 31)) << 1) | (ne << 2);
+    } else {
+      // Termination's bit when term holds, else Invariant2's fail bit (slot 3)
+      const uint32_t tk = opaque_uniform(term ? (1u << PSG_MAX_CHECKS) : (1u << 3));
+      // anyD && cnt <= 2n/3: the AND of two sign bits (-|D| < 0 iff someone decided)
+      const uint32_t f1 = (les & opaque_uniform((uint32_t)-mpopc(D))) >> 31;
+      fb = tk | (f1 & (tk >> 3)) | (f1 << 1) | (ne << 2);
+    }
+    ck.record(fb, false, c, g.lane);
+    return;
+  }
   bool keep = true, validity = true, same = true, irrev = true;
-  if (wany) {  // exact resolution, one ballot per formula
+  if (wany) {  // some process is a possible witness: exact resolution, one ballot per formula
     if constexpr (!V2) keep = X0.all_in(g, full, x);
     validity = X0.all_in(g, D, decision);
     same = !many(mand(D, g.ballot(decision != d0)));
     if (has_old) irrev = !many(mandn(g.ballot(old01 != 0u), mand(D, g.ballot(old_decision == decision))));
   }
-  // the vote count's value: d0 once someone decided; before that OTR reads the count only as
-  // cnt == n (Invariant1; Invariant0 is keepInit alone with no decision), which holds iff every
-  // x equals process 0's — the majority candidate is needed only for OTR2's e0 (and W > 1)
-  const int32_t ref = anyD ? d0 : ((!V2 && W == 1) ? readlane32(x, 0) : majority_candidate<W>(g, x));
-  const int cnt = mpopc(g.ballot((valid01 & eq01(x, ref)) != 0u));
+  if constexpr (W > 1) cnt = vote_count();
   const bool condv = !anyD || same;
   const bool e0 = condv && cnt > sthr;
   const bool e1 = condv && cnt == n;
@@ -106,6 +126,54 @@ PSG_DEV void otr_check(Grp<W>& g, OtrLds<W>& L, const X0Set<W>& X0, Checks& ck, 
   const uint32_t fb = fbit(inv0 || inv1 || inv2, 0) | fbit(inv0, 1) | fbit(inv1, 2) | fbit(inv2, 3) |
                       fbit(same, 4) | fbit(validity, 5) | fbit(integrity, 6) | fbit(irrev, 7);
   ck.record(fb, term, c, g.lane);
+}
+
+// The check in the settled state: every process decided, every decision equal to process 0's,
+// no witness: one ballot of a per-process word, with process 0's decision as d0 (when all
+// decided, process 0 is the first decider). Then keepInit, Validity, Agreement and
+// Irrevocability hold, so Invariant2 (OTR: term && all decisions equal and initial; OTR2: all
+// decisions equal), Safety and Integrity hold; Invariant0 reduces to e0 (OTR2: term),
+// Invariant1 to e1, with the vote count taken at v = d0: the same values as the general path,
+// in a few instructions (most check points of a run are in this state). The results depend on
+// the count alone and are recorded per lane against ckthr (no scalar fail word): slot 1 fails
+// iff cnt <= 2n/3 (OTR), slot 2 iff cnt <= n - 1 (cnt <= n always), Termination holds, no
+// other slot fails. Returns false, with nothing recorded, when the state is not settled.
+template <int W, bool V2>
+PSG_DEV bool otr_check_settled(Grp<W>& g, OtrLds<W>& L, Checks& ck, int c, int n, int32_t x, uint32_t dec01,
+                               int32_t decision, uint32_t valid01, uint32_t od, uint32_t ox, uint32_t irr01,
+                               int32_t ckthr) {
+  if constexpr (W > 1) {
+    L.ds[g.pid] = decision;
+    __syncthreads();
+  }
+  const int32_t p0 = g.bcast(decision, L.ds, 0);
+  uint32_t u = (1u - dec01) | od | ne01(decision, p0) | irr01;
+  if constexpr (!V2) u |= ox;  // keepInit (OTR only)
+  if (g.any((u & valid01) != 0u)) return false;
+  const int cnt = mpopc(g.ballot(x == p0));  // (a compare and the valid-lane mask)
+  if constexpr (W == 1) {
+    ck.record_le(cnt, ckthr, c);
+  } else {  // the same results as a scalar fail word (W > 1: one VGPR fewer, it sits at an occupancy step)
+    const int sthr = (2 * n) / 3;
+    ck.record((V2 ? 0u : fbit(cnt > sthr, 1)) | fbit(cnt == n, 2), true, c, g.lane);
+  }
+  return true;
+}
+
+template <int W, bool V2, bool FROZEN = false>
+// od / ox: "decision / x maybe not initial" (X0Set::maybe_out01_2 of the current values), probed
+// by the caller when the values change (round 0 and executed updates) instead of at every check
+// point: the memoized probe of the fused lowering (DESIGN §5); every formula is still evaluated.
+// FROZEN: a check point of the frozen tail, where the pre-round state is the current one, so the
+// Irrevocability witness old.decided && !(decided && old.decision == decision) is 0 by algebra.
+// ckthr: the settled state's per-lane record thresholds (otr_check_thresholds), formed once per kernel.
+PSG_DEV void otr_check(Grp<W>& g, OtrLds<W>& L, const X0Set<W>& X0, Checks& ck, int c, bool has_old, int n,
+                       const Mask<W>& full, int32_t x, uint32_t dec01, int32_t decision, uint32_t old01,
+                       int32_t old_decision, uint32_t valid01, uint32_t od, uint32_t ox, int32_t ckthr) {
+  const uint32_t irr01 = (has_old && !FROZEN) ? old01 & (1u - (dec01 & eq01(old_decision, decision))) : 0u;
+  if (!otr_check_settled<W, V2>(g, L, ck, c, n, x, dec01, decision, valid01, od, ox, irr01, ckthr))
+    otr_check_general<W, V2>(g, L, X0, ck, c, has_old, n, full, x, dec01, decision, old01, old_decision, valid01, od,
+                             ox, irr01);
 }
 
 // Kernel body; SH = NoHook for the library's kernels, spec::SpecHook<GenSpec> in a
@@ -129,6 +197,7 @@ PSG_DEV void otr_body(const KArgs& a) {
   const int thr = a.variant == 1 ? n / 2 : (2 * n) / 3;  // Otr.scala:64, 67 (variant 1: mutation)
   const Mask<W> full = mfull<W>(n);
   const uint32_t valid01 = g.valid ? 1u : 0u;
+  const int32_t ckthr = W == 1 ? otr_check_thresholds<V2>(n, g.lane) : 0;  // (W > 1: unused)
 
   PhaseTimers pt;  // profiling builds only: t0 setup, t1 active round, t2 frozen round, t3 finish
   pt.start();
@@ -168,7 +237,7 @@ PSG_DEV void otr_body(const KArgs& a) {
     Checks ck;
     ck.reset();
     typename SH::template State<W> sh(g, grp, n);  // fused Spec evaluation state (NoHook: empty)
-    if constexpr (!SH::kFused) otr_check<W, V2>(g, L, X0, ck, 0, false, n, full, x, dec01, decision, 0u, -1, valid01, od, ox);
+    if constexpr (!SH::kFused) otr_check<W, V2>(g, L, X0, ck, 0, false, n, full, x, dec01, decision, 0u, -1, valid01, od, ox, ckthr);
     // OTR2's decision is an Option (PSG_NONE32 when empty)
     auto trace = [&](int c, int32_t hs, bool frozen = false) {
       emit_state<W, SH>(sh, g, a, i, c, x, (int32_t)dec01, V2 && !dec01 ? PSG_NONE32 : decision, 0, 0, 0, 0, 0, hs,
@@ -287,7 +356,7 @@ PSG_DEV void otr_body(const KArgs& a) {
         halted01 |= h;
       }
       if constexpr (!SH::kFused)
-        otr_check<W, V2>(g, L, X0, ck, k + 1, true, n, full, x, dec01, decision, old01, old_decision, valid01, od, ox);
+        otr_check<W, V2>(g, L, X0, ck, k + 1, true, n, full, x, dec01, decision, old01, old_decision, valid01, od, ox, ckthr);
       if (tracing_on) trace(k + 1, hs);
       pt.mark(1);
     }
@@ -296,7 +365,7 @@ PSG_DEV void otr_body(const KArgs& a) {
     // these check points, kf + 1 .. R (Otr.scala:95-120 over the frozen state).
     for (int k = kf; k < a.R; ++k) {
       if constexpr (!SH::kFused)
-        otr_check<W, V2, true>(g, L, X0, ck, k + 1, true, n, full, x, dec01, decision, dec01, decision, valid01, od, ox);
+        otr_check<W, V2, true>(g, L, X0, ck, k + 1, true, n, full, x, dec01, decision, dec01, decision, valid01, od, ox, ckthr);
       if (tracing_on) trace(k + 1, n, true);
       pt.mark(2);
     }
