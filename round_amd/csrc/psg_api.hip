@@ -141,6 +141,12 @@ static const char* const k_names_lv[] = {"Safety", "Invariant0", "Invariant1", "
 static const char* const k_names_benor[] = {"Safety", "Invariant0", "Agreement", "Irrevocability", "SafetyPredicate"};
 static const char* const k_names_k[] = {"KAgreement", "KValidity"};
 static const char* const k_names_eps[] = {"EpsAgreement", "EpsValidity", "SafetyPredicate"};
+// the kernels record and flush exactly the named slots (psg_device.hpp)
+static_assert(std::size(k_names_otr) == kOtrChecks, "k_names_otr and kOtrChecks disagree");
+static_assert(std::size(k_names_lv) == kLvChecks, "k_names_lv and kLvChecks disagree");
+static_assert(std::size(k_names_benor) == kBenOrChecks, "k_names_benor and kBenOrChecks disagree");
+static_assert(std::size(k_names_k) == kKAgreeChecks, "k_names_k and kKAgreeChecks disagree");
+static_assert(std::size(k_names_eps) == kEpsilonChecks, "k_names_eps and kEpsilonChecks disagree");
 
 struct CheckNames {
   const char* const* name;

@@ -193,7 +193,7 @@ PSG_DEV void benor_fast(Grp<W>& g, const KArgs& a, uint64_t i, SC& sc, CrashSets
     }
     check(k + 1, true);
   }
-  finish_instance<W>(g, a, i, ck, 5, dec_val, dec_round, halt_round, x ? 1 : 0, bc);
+  finish_instance<W>(g, a, i, ck, kBenOrChecks, dec_val, dec_round, halt_round, x ? 1 : 0, bc);
 }
 
 // ---------------------------------------------------------------- built-in checker, lane-packed
@@ -348,7 +348,7 @@ PSG_DEV void benor_packed(const Pk<W>& P, const KArgs& a, uint64_t i, uint64_t i
   int32_t fx[W];
 #pragma unroll
   for (int j = 0; j < W; ++j) fx[j] = (int32_t)x[j];
-  pk_finish<W, false>(P, a, i, ck, 5, dec_val, dec_round, halt_round, fx, bc);
+  pk_finish<W, false>(P, a, i, ck, kBenOrChecks, dec_val, dec_round, halt_round, fx, bc);
 }
 
 #ifndef PSG_BO_PK_WPE
@@ -362,16 +362,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PSG_BO
   Pk<W> P;
   P.setup(a.n);
   InstanceQueue<1> Q;
-  for (uint64_t i = Q.take(a); i != Q.kDone; i = Q.take(a)) {
-    const uint64_t inst = a.ids ? a.ids[i] : a.inst_begin + i;
-    benor_packed<W>(P, a, i, inst, &bc);
-  }
+  for (uint64_t i = Q.take(a); i != Q.kDone; i = Q.take(a)) benor_packed<W>(P, a, i, instance_id(a, i), &bc);
   __syncthreads();
-  counters_flush(&bc, a.counters, 5, a.R);
+  counters_flush(&bc, a.counters, kBenOrChecks, a.R);
 }
 
-// Kernel body; SH = NoHook for the library's kernels, spec::SpecHook<GenSpec> in a
-// fused Spec module (round_amd/formula.py compile_native(fused=True)).
+// Kernel body; SH: the Spec hook (NoHook in psg_device.hpp).
 template <int W, bool XHO, class SH = NoHook>
 PSG_DEV void benor_body(const KArgs& a) {
   __shared__ BlockCounters bc;
@@ -392,7 +388,7 @@ PSG_DEV void benor_body(const KArgs& a) {
   pt.start();
   InstanceQueue<W> Q;  // dynamic instance distribution (psg_device.hpp)
   for (uint64_t i = Q.take(a); i != Q.kDone; i = Q.take(a)) {
-    const uint64_t inst = a.ids ? a.ids[i] : a.inst_begin + i;
+    const uint64_t inst = instance_id(a, i);
     Sched<W, XHO> sc;
     sc.setup(a, inst, g.pid, g.valid);
     CrashSets<W> cs;  // per-instance crash rounds (no per-round exchange for W > 1)
@@ -491,12 +487,12 @@ PSG_DEV void benor_body(const KArgs& a) {
       if (tracing<SH>(a)) trace(k + 1, hs);
       pt.mark(many(act) ? 4 : 5);
     }
-    finish_instance<W>(g, a, i, SH::kFused ? sh.ck : ck, SH::kFused ? SH::kSlots : 5, dec_val, dec_round, halt_round, x ? 1 : 0, &bc);
+    finish_instance<W>(g, a, i, hook_checks<SH>(sh, ck), hook_slots<SH>(kBenOrChecks), dec_val, dec_round, halt_round, x ? 1 : 0, &bc);
     pt.mark(3);
   }
   pt.flush(a.counters, threadIdx.x & 63);
   __syncthreads();
-  counters_flush(&bc, a.counters, SH::kFused ? SH::kSlots : 5, a.R);
+  counters_flush(&bc, a.counters, hook_slots<SH>(kBenOrChecks), a.R);
 }
 
 #ifndef PSG_BENOR_WPE
@@ -512,15 +508,10 @@ benor_kernel(KArgs a) {
 template <int W>
 static hipError_t launch_w(const KArgs& a, int grid, hipStream_t s) {
   if constexpr (W > 1) {  // seeded schedule, built-in checker: lane-packed path
-    if (!a.ho_in && !a.trace) {
-      const int pg = pk_grid<PSG_ALG_BENOR, W>((const void*)benor_packed_kernel<W>, a.count);
-      hipLaunchKernelGGL((benor_packed_kernel<W>), dim3(pg), dim3(256), 0, s, a);
-      return hipGetLastError();
-    }
+    if (!a.ho_in && !a.trace) return launch_pk<PSG_ALG_BENOR, W>(benor_packed_kernel<W>, a, s);
   }
-  if (a.ho_in) hipLaunchKernelGGL((benor_kernel<W, true>), dim3(grid), dim3(Geometry<W>::kThreads), 0, s, a);
-  else hipLaunchKernelGGL((benor_kernel<W, false>), dim3(grid), dim3(Geometry<W>::kThreads), 0, s, a);
-  return hipGetLastError();
+  if (a.ho_in) return launch_grp<W>(benor_kernel<W, true>, a, grid, s);
+  return launch_grp<W>(benor_kernel<W, false>, a, grid, s);
 }
 
 hipError_t launch_benor(const KArgs& a, int W, int grid, hipStream_t s) {

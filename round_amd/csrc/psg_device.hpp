@@ -76,6 +76,8 @@ struct KArgs {
   int32_t* hand_dec;
 };
 
+// Global instance id of batch element i: the explicit id list, else consecutive ids.
+PSG_DEV uint64_t instance_id(const KArgs& a, uint64_t i) { return a.ids ? a.ids[i] : a.inst_begin + i; }
 // Initial value of process pid of batch element i (global id inst): staged rows
 // are indexed by batch position, or by global id in the fetch (ids) path.
 PSG_DEV uint64_t init_row(const KArgs& a, uint64_t i, uint64_t inst) { return a.ids ? inst - a.init_base : i; }
@@ -1156,6 +1158,28 @@ struct CrashSets {
   }
 };
 
+// Per-instance prologue of the group-path bodies, in its fixed order: the crash draw (setup), the
+// crash sets (before the first round), the first block of good rounds. FloodMin, KSet, BenOr and
+// Epsilon write the same calls out: behind begin() their kernels compile differently.
+template <int W, bool XHO>
+struct Inst {
+  uint64_t id;  // global instance id
+  Sched<W, XHO> sc;
+  CrashSets<W> cs;  // per-instance crash rounds (no per-round exchange for W > 1)
+  // crl: 64*W words of LDS (W > 1); call from uniform control flow
+  PSG_DEV void begin(Grp<W>& g, const KArgs& a, uint64_t i, int32_t* crl) {
+    id = instance_id(a, i);
+    sc.setup(a, id, g.pid, g.valid);
+    if (sc.crash_on) cs.prep(g, crl, sc.crash_round);
+    sc.prep_good(0, g.lane, a.R);
+  }
+  // Initial value of this lane's process: host-supplied, else seeded (0 for lanes past n)
+  PSG_DEV int32_t x0(const Grp<W>& g, const KArgs& a, uint64_t i, int alg) const {
+    if (!g.valid) return 0;
+    return a.init ? init_x(a, i, id, g.pid) : sc.init_value(g.pid, alg);
+  }
+};
+
 // ---------------------------------------------------------------- per-instance checks
 struct Checks {
   // One VGPR: lane s (< PSG_MAX_CHECKS) holds slot s's first failing check point, lane
@@ -1319,7 +1343,8 @@ PSG_DEV void trace_put(const Grp<W>& g, const KArgs& a, uint64_t i, int c, int32
 // Spec hooks of the round kernels. NoHook: the built-in checks (+ the trace of
 // psg_run_batch_spec). A fused Spec module (round_amd/formula.py
 // compile_native(fused=True), psg_spec_native.hpp spec::SpecHook) instead
-// evaluates a compiled Spec at every check point from the kernel's registers.
+// evaluates a compiled Spec at every check point from the kernel's registers. The kernel
+// bodies take the hook as template parameter SH (a fused module: spec::SpecHook<GenSpec>).
 struct NoHook {
   static constexpr bool kFused = false;
   static constexpr int kSlots = 0;
@@ -1331,6 +1356,19 @@ struct NoHook {
     PSG_DEV void put(int, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t) {}
   };
 };
+
+// Built-in checks per algorithm family: the slots its kernels record and flush, and the length
+// of its name table in psg_api.hip (static_assert there).
+constexpr int kOtrChecks = 8;      // OTR, OTR2
+constexpr int kLvChecks = 7;       // LastVoting
+constexpr int kBenOrChecks = 5;    // BenOr
+constexpr int kKAgreeChecks = 2;   // FloodMin, KSet, ShortLastVoting, KSetEarlyStopping
+constexpr int kEpsilonChecks = 3;  // EpsilonConsensus
+// The check slots and the Checks a kernel with hook SH reports: the fused Spec's, else the built-in ones.
+template <class SH>
+PSG_DEV constexpr int hook_slots(int builtin) { return SH::kFused ? SH::kSlots : builtin; }
+template <class SH, class St>
+PSG_DEV const Checks& hook_checks(const St& sh, const Checks& ck) { return SH::kFused ? sh.ck : ck; }
 
 // Is the process state of every check point needed (trace or fused Spec)? TR = false: the
 // launch has no Spec-program trace (known at compile time: the instantiation the library's
@@ -1356,6 +1394,14 @@ struct Geometry {
   static constexpr int kThreads = W == 1 ? 256 : 64 * W;
   static constexpr int kGroups = W == 1 ? 4 : 1;
 };
+
+#if !defined(__HIPCC_RTC__) && !defined(PSG_FUSED_MODULE)  // host: launch of a group-geometry kernel
+template <int W, class K, class... More>
+static hipError_t launch_grp(K kernel, const KArgs& a, int grid, hipStream_t s, More... more) {
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(Geometry<W>::kThreads), 0, s, a, more...);
+  return hipGetLastError();
+}
+#endif
 
 template <int W>
 PSG_DEV void grp_setup(Grp<W>& g, const KArgs& a, uint64_t* xb, int64_t* red) {

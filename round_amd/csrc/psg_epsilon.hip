@@ -345,7 +345,7 @@ epsilon_kernel(KArgs a) {
 
   InstanceQueue<W> Q;  // dynamic instance distribution (psg_device.hpp)
   for (uint64_t i = Q.take(a); i != Q.kDone; i = Q.take(a)) {
-    const uint64_t inst = a.ids ? a.ids[i] : a.inst_begin + i;
+    const uint64_t inst = instance_id(a, i);
     Sched<W, XHO> sc;
     sc.setup(a, inst, g.pid, g.valid);
     CrashSets<W> cs;  // per-instance crash rounds (no per-round exchange for W > 1)
@@ -514,17 +514,16 @@ epsilon_kernel(KArgs a) {
         a.out_rec_f64[2 * off + 1] = x;
       }
     }
-    finish_instance<W>(g, a, i, ck, 3, decided ? fold32d(decision) : 0, dec_round, halt_round, fold32d(x), &bc);
+    finish_instance<W>(g, a, i, ck, kEpsilonChecks, decided ? fold32d(decision) : 0, dec_round, halt_round, fold32d(x), &bc);
   }
   __syncthreads();
-  counters_flush(&bc, a.counters, 3, a.R);
+  counters_flush(&bc, a.counters, kEpsilonChecks, a.R);
 }
 
 template <int W>
 static hipError_t launch_w(const KArgs& a, int grid, hipStream_t s) {
-  if (a.ho_in) hipLaunchKernelGGL((epsilon_kernel<W, true>), dim3(grid), dim3(Geometry<W>::kThreads), 0, s, a);
-  else hipLaunchKernelGGL((epsilon_kernel<W, false>), dim3(grid), dim3(Geometry<W>::kThreads), 0, s, a);
-  return hipGetLastError();
+  if (a.ho_in) return launch_grp<W>(epsilon_kernel<W, true>, a, grid, s);
+  return launch_grp<W>(epsilon_kernel<W, false>, a, grid, s);
 }
 
 hipError_t launch_epsilon(const KArgs& a, int W, int grid, hipStream_t s) {

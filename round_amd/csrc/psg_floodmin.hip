@@ -154,7 +154,7 @@ PSG_DEV void floodmin_fast(Grp<W>& g, const KArgs& a, uint64_t i, SC& sc, CrashS
     }
     check(k + 1);
   }
-  finish_instance<W>(g, a, i, ck, 2, dec_val, dec_round, halt_round, x, bc);
+  finish_instance<W>(g, a, i, ck, kKAgreeChecks, dec_val, dec_round, halt_round, x, bc);
 }
 
 // ---------------------------------------------------------------- crash-stop fast path, lane-packed
@@ -270,7 +270,7 @@ PSG_DEV void floodmin_packed(const Pk<W>& P, const KArgs& a, uint64_t i, uint64_
     dv[j] = dk >= 0 ? x[j] : 0;
     dr[j] = dk;
   }
-  pk_finish<W>(P, a, i, ck, 2, dv, dr, dr, x, bc);
+  pk_finish<W>(P, a, i, ck, kKAgreeChecks, dv, dr, dr, x, bc);
 }
 
 template <int W>
@@ -283,16 +283,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PSG_PK
   P.setup(a.n);
   int32_t* x0lds = x0tab[threadIdx.x >> 6];
   InstanceQueue<1> Q;
-  for (uint64_t i = Q.take(a); i != Q.kDone; i = Q.take(a)) {
-    const uint64_t inst = a.ids ? a.ids[i] : a.inst_begin + i;
-    floodmin_packed<W>(P, a, i, inst, x0lds, &bc);
-  }
+  for (uint64_t i = Q.take(a); i != Q.kDone; i = Q.take(a)) floodmin_packed<W>(P, a, i, instance_id(a, i), x0lds, &bc);
   __syncthreads();
-  counters_flush(&bc, a.counters, 2, a.R);
+  counters_flush(&bc, a.counters, kKAgreeChecks, a.R);
 }
 
-// Kernel body; SH = NoHook for the library's kernels, spec::SpecHook<GenSpec> in a
-// fused Spec module (round_amd/formula.py compile_native(fused=True)).
+// Kernel body; SH: the Spec hook (NoHook in psg_device.hpp).
 template <int W, bool XHO, class SH = NoHook>
 PSG_DEV void floodmin_body(const KArgs& a) {
   __shared__ BlockCounters bc;
@@ -315,7 +311,7 @@ PSG_DEV void floodmin_body(const KArgs& a) {
   pt.start();
   InstanceQueue<W> Q;  // dynamic instance distribution (psg_device.hpp)
   for (uint64_t i = Q.take(a); i != Q.kDone; i = Q.take(a)) {
-    const uint64_t inst = a.ids ? a.ids[i] : a.inst_begin + i;
+    const uint64_t inst = instance_id(a, i);
     Sched<W, XHO> sc;
     sc.setup(a, inst, g.pid, g.valid);
     CrashSets<W> cs;  // per-instance crash rounds (no per-round exchange for W > 1)
@@ -412,12 +408,12 @@ PSG_DEV void floodmin_body(const KArgs& a) {
       if (tracing<SH>(a)) trace(k + 1, hs);
       pt.mark(many(act) ? 4 : 5);
     }
-    finish_instance<W>(g, a, i, SH::kFused ? sh.ck : ck, SH::kFused ? SH::kSlots : 2, dec_val, dec_round, halt_round, x, &bc);
+    finish_instance<W>(g, a, i, hook_checks<SH>(sh, ck), hook_slots<SH>(kKAgreeChecks), dec_val, dec_round, halt_round, x, &bc);
     pt.mark(3);
   }
   pt.flush(a.counters, threadIdx.x & 63);
   __syncthreads();
-  counters_flush(&bc, a.counters, SH::kFused ? SH::kSlots : 2, a.R);
+  counters_flush(&bc, a.counters, hook_slots<SH>(kKAgreeChecks), a.R);
 }
 
 #ifndef PSG_FM_WPE
@@ -433,15 +429,11 @@ floodmin_kernel(KArgs a) {
 template <int W>
 static hipError_t launch_w(const KArgs& a, int grid, hipStream_t s) {
   if constexpr (W > 1) {  // seeded crash-stop schedule, built-in checker: lane-packed fast path
-    if (!a.ho_in && !a.trace && a.drop_log2 == 0 && a.good_p32 == 0 && a.ho_min < 0) {
-      const int pg = pk_grid<PSG_ALG_FLOODMIN, W>((const void*)floodmin_packed_kernel<W>, a.count);
-      hipLaunchKernelGGL((floodmin_packed_kernel<W>), dim3(pg), dim3(256), 0, s, a);
-      return hipGetLastError();
-    }
+    if (!a.ho_in && !a.trace && a.drop_log2 == 0 && a.good_p32 == 0 && a.ho_min < 0)
+      return launch_pk<PSG_ALG_FLOODMIN, W>(floodmin_packed_kernel<W>, a, s);
   }
-  if (a.ho_in) hipLaunchKernelGGL((floodmin_kernel<W, true>), dim3(grid), dim3(Geometry<W>::kThreads), 0, s, a);
-  else hipLaunchKernelGGL((floodmin_kernel<W, false>), dim3(grid), dim3(Geometry<W>::kThreads), 0, s, a);
-  return hipGetLastError();
+  if (a.ho_in) return launch_grp<W>(floodmin_kernel<W, true>, a, grid, s);
+  return launch_grp<W>(floodmin_kernel<W, false>, a, grid, s);
 }
 
 hipError_t launch_floodmin(const KArgs& a, int W, int grid, hipStream_t s) {

@@ -570,7 +570,7 @@ PSG_DEV void kset_packed(const Pk<W>& P, const KArgs& a, uint64_t i, uint64_t in
   int32_t mainx[W];
 #pragma unroll
   for (int j = 0; j < W; ++j) mainx[j] = P.val[j] ? kset_pick<W>(t[j], L.x0s, Emin, xmin) : 0;
-  pk_finish<W>(P, a, i, ck, 2, decision, halt_round, halt_round, mainx, bc);
+  pk_finish<W>(P, a, i, ck, kKAgreeChecks, decision, halt_round, halt_round, mainx, bc);
   if constexpr (HAND) {
     if (P.lane == 0) a.hand_hdr[i] = kHandDone;
   }
@@ -733,7 +733,7 @@ PSG_DEV void kset_tail(const Pk<W>& P, const KArgs& a, uint64_t i, uint64_t inst
   int32_t mainx[W];
 #pragma unroll
   for (int j = 0; j < W; ++j) mainx[j] = (halt_round[j] >= 0 && halt_round[j] < k0) ? decision[j] : pu;
-  pk_finish<W>(P, a, i, ck, 2, decision, halt_round, halt_round, mainx, bc);
+  pk_finish<W>(P, a, i, ck, kKAgreeChecks, decision, halt_round, halt_round, mainx, bc);
   pt.mark(3);
 }
 
@@ -760,13 +760,12 @@ kset_packed_kernel(KArgs a) {
   PhaseTimers pt;  // profiling builds only: t0 setup, t1 staging + classes, t2 slot updates, t3 finish,
   pt.start();      // t4 check after a live round, t5 frozen round, t6 the slots' HO sets
   InstanceQueue<1> Q;
-  for (uint64_t i = Q.take(a); i != Q.kDone; i = Q.take(a)) {
-    const uint64_t inst = a.ids ? a.ids[i] : a.inst_begin + i;
-    kset_packed<W, HAND>(P, a, i, inst, L[grp], S, grp * KsStage<W>::kBufs / KsStage<W>::kWaves, x0tab[grp], &bc, pt);
-  }
+  for (uint64_t i = Q.take(a); i != Q.kDone; i = Q.take(a))
+    kset_packed<W, HAND>(P, a, i, instance_id(a, i), L[grp], S, grp * KsStage<W>::kBufs / KsStage<W>::kWaves, x0tab[grp],
+                         &bc, pt);
   pt.flush(a.counters, P.lane);
   __syncthreads();
-  counters_flush(&bc, a.counters, 2, a.R);
+  counters_flush(&bc, a.counters, kKAgreeChecks, a.R);
 }
 
 #ifndef PSG_KSET_TAIL_WPE
@@ -785,16 +784,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LAZY ?
   for (uint64_t i = Q.take(a); i != Q.kDone; i = Q.take(a)) {
     const uint64_t h = a.hand_hdr[i];
     if (h & kHandDone) continue;  // finished by the general kernel
-    const uint64_t inst = a.ids ? a.ids[i] : a.inst_begin + i;
-    kset_tail<W, LAZY>(P, a, i, inst, h, &bc, pt);
+    kset_tail<W, LAZY>(P, a, i, instance_id(a, i), h, &bc, pt);
   }
   pt.flush(a.counters, P.lane);
   __syncthreads();
-  counters_flush(&bc, a.counters, 2, a.R);
+  counters_flush(&bc, a.counters, kKAgreeChecks, a.R);
 }
 
-// Kernel body; SH = NoHook for the library's kernels, spec::SpecHook<GenSpec> in a
-// fused Spec module (round_amd/formula.py compile_native(fused=True)).
+// Kernel body; SH: the Spec hook (NoHook in psg_device.hpp).
 template <int W, bool XHO, class SH = NoHook>
 PSG_DEV void kset_body(const KArgs& a) {
   __shared__ BlockCounters bc;
@@ -820,7 +817,7 @@ PSG_DEV void kset_body(const KArgs& a) {
   pt.start();
   InstanceQueue<W> Q;  // dynamic instance distribution (psg_device.hpp)
   for (uint64_t i = Q.take(a); i != Q.kDone; i = Q.take(a)) {
-    const uint64_t inst = a.ids ? a.ids[i] : a.inst_begin + i;
+    const uint64_t inst = instance_id(a, i);
     Sched<W, XHO> sc;
     sc.setup(a, inst, g.pid, g.valid);
     CrashSets<W> cs;  // per-instance crash rounds (no per-round exchange for W > 1)
@@ -944,13 +941,13 @@ PSG_DEV void kset_body(const KArgs& a) {
       pt.mark(many(act) ? 4 : 5);
     }
     const int32_t mainx = g.valid ? kset_pick<W>(t, x0s, Emin, xmin) : 0;
-    finish_instance<W>(g, a, i, SH::kFused ? sh.ck : ck, SH::kFused ? SH::kSlots : 2, dec_val, dec_round, halt_round, mainx, &bc);
+    finish_instance<W>(g, a, i, hook_checks<SH>(sh, ck), hook_slots<SH>(kKAgreeChecks), dec_val, dec_round, halt_round, mainx, &bc);
     lds_sync<W>();
     pt.mark(3);
   }
   pt.flush(a.counters, threadIdx.x & 63);
   __syncthreads();
-  counters_flush(&bc, a.counters, SH::kFused ? SH::kSlots : 2, a.R);
+  counters_flush(&bc, a.counters, hook_slots<SH>(kKAgreeChecks), a.R);
 }
 
 #ifndef PSG_KSET_WPE
@@ -968,25 +965,16 @@ static hipError_t launch_w(const KArgs& a, int grid, hipStream_t s) {
   if constexpr (W > 1) {  // seeded schedule, built-in checker: lane-packed path
     if (!a.ho_in && !a.trace) {
       if (PSG_KSET_SPLIT && a.hand_hdr) {  // general rounds, then the uniform-t tail (same stream)
-        const int pg = pk_grid<PSG_ALG_KSET, W>((const void*)kset_packed_kernel<W, true>, a.count);
-        hipLaunchKernelGGL((kset_packed_kernel<W, true>), dim3(pg), dim3(256), 0, s, a);
-        if (a.drop_log2 == 0 && a.ho_min < 0) {  // loss-free schedules: uniform mailboxes but crash rounds
-          const int tg = pk_grid<PSG_ALG_KSET | 0x100, W>((const void*)kset_tail_kernel<W, true>, a.count);
-          hipLaunchKernelGGL((kset_tail_kernel<W, true>), dim3(tg), dim3(256), 0, s, a);
-        } else {
-          const int tg = pk_grid<PSG_ALG_KSET | 0x300, W>((const void*)kset_tail_kernel<W, false>, a.count);
-          hipLaunchKernelGGL((kset_tail_kernel<W, false>), dim3(tg), dim3(256), 0, s, a);
-        }
-        return hipGetLastError();
+        if (hipError_t e = launch_pk<PSG_ALG_KSET, W>(kset_packed_kernel<W, true>, a, s)) return e;
+        if (a.drop_log2 == 0 && a.ho_min < 0)  // loss-free schedules: uniform mailboxes but crash rounds
+          return launch_pk<PSG_ALG_KSET | 0x100, W>(kset_tail_kernel<W, true>, a, s);
+        return launch_pk<PSG_ALG_KSET | 0x300, W>(kset_tail_kernel<W, false>, a, s);
       }
-      const int pg = pk_grid<PSG_ALG_KSET | 0x200, W>((const void*)kset_packed_kernel<W, false>, a.count);
-      hipLaunchKernelGGL((kset_packed_kernel<W, false>), dim3(pg), dim3(256), 0, s, a);
-      return hipGetLastError();
+      return launch_pk<PSG_ALG_KSET | 0x200, W>(kset_packed_kernel<W, false>, a, s);
     }
   }
-  if (a.ho_in) hipLaunchKernelGGL((kset_kernel<W, true>), dim3(grid), dim3(Geometry<W>::kThreads), 0, s, a);
-  else hipLaunchKernelGGL((kset_kernel<W, false>), dim3(grid), dim3(Geometry<W>::kThreads), 0, s, a);
-  return hipGetLastError();
+  if (a.ho_in) return launch_grp<W>(kset_kernel<W, true>, a, grid, s);
+  return launch_grp<W>(kset_kernel<W, false>, a, grid, s);
 }
 
 hipError_t launch_kset(const KArgs& a, int W, int grid, hipStream_t s) {

@@ -181,7 +181,7 @@ PSG_DEV void kset_es_packed(const Pk<W>& P, const KArgs& a, uint64_t i, uint64_t
   int32_t halt_round[W];
 #pragma unroll
   for (int j = 0; j < W; ++j) halt_round[j] = (int32_t)(nbh[j] >> 16) - 1;
-  pk_finish<W>(P, a, i, ck, 2, decision, halt_round, halt_round, est, bc);
+  pk_finish<W>(P, a, i, ck, kKAgreeChecks, decision, halt_round, halt_round, est, bc);
 }
 
 #ifndef PSG_KSETES_PK_WPE
@@ -197,16 +197,13 @@ kset_es_packed_kernel(KArgs a) {
   Pk<W> P;
   P.setup(a.n);
   InstanceQueue<1> Q;
-  for (uint64_t i = Q.take(a); i != Q.kDone; i = Q.take(a)) {
-    const uint64_t inst = a.ids ? a.ids[i] : a.inst_begin + i;
-    kset_es_packed<W>(P, a, i, inst, x0tab[threadIdx.x >> 6], &bc);
-  }
+  for (uint64_t i = Q.take(a); i != Q.kDone; i = Q.take(a))
+    kset_es_packed<W>(P, a, i, instance_id(a, i), x0tab[threadIdx.x >> 6], &bc);
   __syncthreads();
-  counters_flush(&bc, a.counters, 2, a.R);
+  counters_flush(&bc, a.counters, kKAgreeChecks, a.R);
 }
 
-// Kernel body; SH = NoHook for the library's kernels, spec::SpecHook<GenSpec> in a
-// fused Spec module (round_amd/formula.py compile_native(fused=True)).
+// Kernel body; SH: the Spec hook (NoHook in psg_device.hpp).
 template <int W, bool XHO, class SH = NoHook>
 PSG_DEV void kset_es_body(const KArgs& a) {
   __shared__ BlockCounters bc;
@@ -226,15 +223,11 @@ PSG_DEV void kset_es_body(const KArgs& a) {
 
   InstanceQueue<W> Q;  // dynamic instance distribution (psg_device.hpp)
   for (uint64_t i = Q.take(a); i != Q.kDone; i = Q.take(a)) {
-    const uint64_t inst = a.ids ? a.ids[i] : a.inst_begin + i;
-    Sched<W, XHO> sc;
-    sc.setup(a, inst, g.pid, g.valid);
-    CrashSets<W> cs;  // per-instance crash rounds (no per-round exchange for W > 1)
-    if (sc.crash_on) cs.prep(g, crl, sc.crash_round);
-    sc.prep_good(0, g.lane, a.R);
+    Inst<W, XHO> in;
+    in.begin(g, a, i, crl);
+    Sched<W, XHO>& sc = in.sc;
     const bool crashed = sc.crash_round >= 0;
-    int32_t x0 = 0;
-    if (g.valid) x0 = a.init ? init_x(a, i, inst, g.pid) : sc.init_value(g.pid, PSG_ALG_KSET_ES);
+    const int32_t x0 = in.x0(g, a, i, PSG_ALG_KSET_ES);
     X0Set<W> X0;
     X0.build(g, x0tab[grp], x0);
     // KSetESProcess state after init(io) (KSetEarlyStopping.scala:16-21)
@@ -267,7 +260,7 @@ PSG_DEV void kset_es_body(const KArgs& a) {
         Mask<W> goodS;
         const bool good = sc.good_round(k, g.lane, a.R, goodS);
         Mask<W> CB = mzero<W>(), CN = mzero<W>();
-        if (sc.crash_on) cs.sets(g, k, CB, CN);
+        if (sc.crash_on) in.cs.sets(g, k, CB, CN);
         const Mask<W> M = mand(sc.ho(k, g.pid, good, goodS, CB, CN), act);
         const int currNb = mpopc(M);
         if (!halted) hs = currNb;
@@ -309,10 +302,10 @@ PSG_DEV void kset_es_body(const KArgs& a) {
       if constexpr (!SH::kFused) check(k + 1);
       if (tracing<SH>(a)) trace(k + 1, hs);
     }
-    finish_instance<W>(g, a, i, SH::kFused ? sh.ck : ck, SH::kFused ? SH::kSlots : 2, dec_val, dec_round, halt_round, est, &bc);
+    finish_instance<W>(g, a, i, hook_checks<SH>(sh, ck), hook_slots<SH>(kKAgreeChecks), dec_val, dec_round, halt_round, est, &bc);
   }
   __syncthreads();
-  counters_flush(&bc, a.counters, SH::kFused ? SH::kSlots : 2, a.R);
+  counters_flush(&bc, a.counters, hook_slots<SH>(kKAgreeChecks), a.R);
 }
 
 #ifndef PSG_KSETES_WPE
@@ -328,15 +321,10 @@ kset_es_kernel(KArgs a) {
 template <int W>
 static hipError_t launch_w(const KArgs& a, int grid, hipStream_t s) {
   if constexpr (W > 1) {  // seeded schedule, built-in checker: lane-packed path
-    if (!a.ho_in && !a.trace) {
-      const int pg = pk_grid<PSG_ALG_KSET_ES, W>((const void*)kset_es_packed_kernel<W>, a.count);
-      hipLaunchKernelGGL((kset_es_packed_kernel<W>), dim3(pg), dim3(256), 0, s, a);
-      return hipGetLastError();
-    }
+    if (!a.ho_in && !a.trace) return launch_pk<PSG_ALG_KSET_ES, W>(kset_es_packed_kernel<W>, a, s);
   }
-  if (a.ho_in) hipLaunchKernelGGL((kset_es_kernel<W, true>), dim3(grid), dim3(Geometry<W>::kThreads), 0, s, a);
-  else hipLaunchKernelGGL((kset_es_kernel<W, false>), dim3(grid), dim3(Geometry<W>::kThreads), 0, s, a);
-  return hipGetLastError();
+  if (a.ho_in) return launch_grp<W>(kset_es_kernel<W, true>, a, grid, s);
+  return launch_grp<W>(kset_es_kernel<W, false>, a, grid, s);
 }
 
 hipError_t launch_kset_es(const KArgs& a, int W, int grid, hipStream_t s) {

@@ -222,8 +222,7 @@ struct CoordWords {
   }
 };
 
-// Kernel body; SH = NoHook for the library's kernels, spec::SpecHook<GenSpec> in a
-// fused Spec module (round_amd/formula.py compile_native(fused=True)).
+// Kernel body; SH: the Spec hook (NoHook in psg_device.hpp).
 template <int W, bool XHO, class SH = NoHook, bool TR = true>
 PSG_DEV void lv_body(const KArgs& a) {
   __shared__ BlockCounters bc;
@@ -250,16 +249,12 @@ PSG_DEV void lv_body(const KArgs& a) {
   pt.start();
   InstanceQueue<W, 0, W == 1 ? PSG_QUEUE_CHUNK_LANE : 0> Q;  // dynamic instance distribution (psg_device.hpp)
   for (uint64_t i = Q.take(a); i != Q.kDone; i = Q.take(a)) {
-    const uint64_t inst = a.ids ? a.ids[i] : a.inst_begin + i;
-    Sched<W, XHO> sc;
-    sc.setup(a, inst, g.pid, g.valid);
-    CrashSets<W> cs;  // per-instance crash rounds (no per-round exchange for W > 1)
-    if (sc.crash_on) cs.prep(g, crl, sc.crash_round);
-    sc.prep_good(0, g.lane, a.R);
+    Inst<W, XHO> in;
+    in.begin(g, a, i, crl);
+    Sched<W, XHO>& sc = in.sc;
     CoordWords<W, XHO> cw;
     if constexpr (!XHO) cw.prep(sc, 0, g.lane, n);
-    int32_t x0 = 0;
-    if (g.valid) x0 = a.init ? init_x(a, i, inst, g.pid) : sc.init_value(g.pid, PSG_ALG_LAST_VOTING);
+    const int32_t x0 = in.x0(g, a, i, PSG_ALG_LAST_VOTING);
     X0Set<W> X0;
     X0.build(g, x0tab[grp], x0);
     // LVProcess state after init(io) (LastVoting.scala:82-109)
@@ -295,7 +290,7 @@ PSG_DEV void lv_body(const KArgs& a) {
         Mask<W> goodS;
         const bool good = sc.good_round(k, g.lane, a.R, goodS);
         Mask<W> CB = mzero<W>(), CN = mzero<W>();
-        if (sc.crash_on) cs.sets(g, k, CB, CN);
+        if (sc.crash_on) in.cs.sets(g, k, CB, CN);
         // R1 / R3 read bit coord of every HO(p) (a mailbox of at most the coordinator's
         // message); R0 / R2 only HO(coord)
         constexpr bool coordRound = (RS & 1) == 0;
@@ -411,12 +406,12 @@ PSG_DEV void lv_body(const KArgs& a) {
       }
       pt.mark(5);
     }
-    finish_instance<W>(g, a, i, SH::kFused ? sh.ck : ck, SH::kFused ? SH::kSlots : 7, dec_val, dec_round, halt_round, x, &bc);
+    finish_instance<W>(g, a, i, hook_checks<SH>(sh, ck), hook_slots<SH>(kLvChecks), dec_val, dec_round, halt_round, x, &bc);
     pt.mark(3);
   }
   pt.flush(a.counters, threadIdx.x & 63);
   __syncthreads();
-  counters_flush(&bc, a.counters, SH::kFused ? SH::kSlots : 7, a.R);
+  counters_flush(&bc, a.counters, hook_slots<SH>(kLvChecks), a.R);
 }
 
 #ifndef PSG_LV_WPE
@@ -431,10 +426,9 @@ lv_kernel(KArgs a) {
 #ifndef PSG_FUSED_MODULE  // host launchers (not part of a fused Spec module)
 template <int W>
 static hipError_t launch_w(const KArgs& a, int grid, hipStream_t s) {
-  if (a.ho_in) hipLaunchKernelGGL((lv_kernel<W, true>), dim3(grid), dim3(Geometry<W>::kThreads), 0, s, a);
-  else if (a.trace) hipLaunchKernelGGL((lv_kernel<W, false>), dim3(grid), dim3(Geometry<W>::kThreads), 0, s, a);
-  else hipLaunchKernelGGL((lv_kernel<W, false, NoHook, false>), dim3(grid), dim3(Geometry<W>::kThreads), 0, s, a);
-  return hipGetLastError();
+  if (a.ho_in) return launch_grp<W>(lv_kernel<W, true>, a, grid, s);
+  if (a.trace) return launch_grp<W>(lv_kernel<W, false>, a, grid, s);
+  return launch_grp<W>(lv_kernel<W, false, NoHook, false>, a, grid, s);
 }
 
 hipError_t launch_lv(const KArgs& a, int W, int grid, hipStream_t s) {

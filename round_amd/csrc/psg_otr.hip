@@ -176,9 +176,8 @@ PSG_DEV void otr_check(Grp<W>& g, OtrLds<W>& L, const X0Set<W>& X0, Checks& ck, 
                              ox, irr01);
 }
 
-// Kernel body; SH = NoHook for the library's kernels, spec::SpecHook<GenSpec> in a
-// fused Spec module (round_amd/formula.py compile_native(fused=True)). TR = false: the
-// launch has no Spec-program trace (a.trace == nullptr), known at compile time.
+// Kernel body; SH: the Spec hook (NoHook in psg_device.hpp). TR = false: the launch has no
+// Spec-program trace (a.trace == nullptr), known at compile time.
 template <int W, bool V2, bool XHO, class SH = NoHook, bool TR = true>
 PSG_DEV void otr_body(const KArgs& a) {
   const bool tracing_on = SH::kFused || (TR && a.trace != nullptr);
@@ -208,8 +207,7 @@ PSG_DEV void otr_body(const KArgs& a) {
   // overlaps the current instance's rounds instead of stalling its setup.
   auto load_x0 = [&](uint64_t ii) -> int32_t {
     if (ii == Q.kDone || !a.init || !g.valid) return 0;
-    const uint64_t in_ = a.ids ? a.ids[ii] : a.inst_begin + ii;
-    return a.init[init_row(a, ii, in_) * (uint64_t)n + g.pid];
+    return a.init[init_row(a, ii, instance_id(a, ii)) * (uint64_t)n + g.pid];
   };
   uint64_t inext = Q.take(a);
   int32_t x0next = load_x0(inext);
@@ -218,12 +216,9 @@ PSG_DEV void otr_body(const KArgs& a) {
     const int32_t x0host = x0next;
     inext = Q.take(a);
     x0next = load_x0(inext);
-    const uint64_t inst = a.ids ? a.ids[i] : a.inst_begin + i;
-    Sched<W, XHO> sc;
-    sc.setup(a, inst, g.pid, g.valid);
-    CrashSets<W> cs;  // per-instance crash rounds (no per-round exchange for W > 1)
-    if (sc.crash_on) cs.prep(g, crl, sc.crash_round);
-    sc.prep_good(0, g.lane, a.R);
+    Inst<W, XHO> in;
+    in.begin(g, a, i, crl);
+    Sched<W, XHO>& sc = in.sc;
     int32_t x0 = 0;
     if (g.valid) x0 = a.init ? x0host : sc.init_value(g.pid, PSG_ALG_OTR);
     X0Set<W> X0;
@@ -280,7 +275,7 @@ PSG_DEV void otr_body(const KArgs& a) {
         Mask<W> goodS;
         const bool good = sc.good_round(k, g.lane, a.R, goodS);
         Mask<W> CB = mzero<W>(), CN = mzero<W>();
-        if (sc.crash_on) cs.sets(g, k, CB, CN);
+        if (sc.crash_on) in.cs.sets(g, k, CB, CN);
         // mailbox: broadcast(x) from every alive sender in HO(p)
         const Mask<W> M = mand(sc.ho(k, g.pid, good, goodS, CB, CN), act);
         const int32_t msize = mpopc(M);
@@ -369,14 +364,14 @@ PSG_DEV void otr_body(const KArgs& a) {
       if (tracing_on) trace(k + 1, n, true);
       pt.mark(2);
     }
-    finish_instance<W>(g, a, i, SH::kFused ? sh.ck : ck, SH::kFused ? SH::kSlots : 8, dec_val, dec_round, halt_round, x, &bc,
+    finish_instance<W>(g, a, i, hook_checks<SH>(sh, ck), hook_slots<SH>(kOtrChecks), dec_val, dec_round, halt_round, x, &bc,
                        &tally, live_rounds);
     pt.mark(3);
   }
   pt.flush(a.counters, threadIdx.x & 63);
   tally.flush(&bc);
   __syncthreads();
-  counters_flush(&bc, a.counters, SH::kFused ? SH::kSlots : 8, a.R);
+  counters_flush(&bc, a.counters, hook_slots<SH>(kOtrChecks), a.R);
 }
 
 #ifndef PSG_OTR_WPE
@@ -391,10 +386,9 @@ otr_kernel(KArgs a) {
 #ifndef PSG_FUSED_MODULE  // host launchers (not part of a fused Spec module)
 template <int W, bool V2>
 static hipError_t launch_w(const KArgs& a, int grid, hipStream_t s) {
-  if (a.ho_in) hipLaunchKernelGGL((otr_kernel<W, V2, true>), dim3(grid), dim3(Geometry<W>::kThreads), 0, s, a);
-  else if (a.trace) hipLaunchKernelGGL((otr_kernel<W, V2, false>), dim3(grid), dim3(Geometry<W>::kThreads), 0, s, a);
-  else hipLaunchKernelGGL((otr_kernel<W, V2, false, NoHook, false>), dim3(grid), dim3(Geometry<W>::kThreads), 0, s, a);
-  return hipGetLastError();
+  if (a.ho_in) return launch_grp<W>(otr_kernel<W, V2, true>, a, grid, s);
+  if (a.trace) return launch_grp<W>(otr_kernel<W, V2, false>, a, grid, s);
+  return launch_grp<W>(otr_kernel<W, V2, false, NoHook, false>, a, grid, s);
 }
 
 template <bool V2>

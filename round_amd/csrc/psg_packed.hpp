@@ -240,6 +240,13 @@ static int pk_grid(const void* kernel, uint64_t count) {
   const uint64_t want = (count + 3) / 4;
   return (int)(want < (uint64_t)resident ? (want < 1 ? 1 : want) : (uint64_t)resident);
 }
+// Launch of a packed kernel on its resident grid; KEY: the kernel's pk_grid cache key.
+template <int KEY, int W, class K>
+static hipError_t launch_pk(K kernel, const KArgs& a, hipStream_t s) {
+  const int pg = pk_grid<KEY, W>((const void*)kernel, a.count);
+  hipLaunchKernelGGL(kernel, dim3(pg), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
 #endif  // PSG_FUSED_MODULE
 
 }  // namespace psg

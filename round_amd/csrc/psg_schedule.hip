@@ -48,10 +48,8 @@ __global__ void __launch_bounds__(Geometry<W>::kThreads) schedule_kernel(KArgs a
 }
 
 hipError_t launch_schedule(const KArgs& a, int W, int grid, uint64_t* ho_out, int32_t* crash_out, hipStream_t s) {
-  return with_w(W, hipErrorInvalidValue, [&](auto w) {
-    hipLaunchKernelGGL(schedule_kernel<w()>, dim3(grid), dim3(Geometry<w()>::kThreads), 0, s, a, ho_out, crash_out);
-    return hipGetLastError();
-  });
+  return with_w(W, hipErrorInvalidValue,
+                [&](auto w) { return launch_grp<w()>(schedule_kernel<w()>, a, grid, s, ho_out, crash_out); });
 }
 
 }  // namespace psg

@@ -55,8 +55,7 @@ PSG_DEV Mask<W> slv_ho_of(Grp<W>& g, SlvLds<W>& L, const Mask<W>& ho, int c) {
   return m;
 }
 
-// Kernel body; SH = NoHook for the library's kernels, spec::SpecHook<GenSpec> in a
-// fused Spec module (round_amd/formula.py compile_native(fused=True)).
+// Kernel body; SH: the Spec hook (NoHook in psg_device.hpp).
 template <int W, bool XHO, class SH = NoHook, bool TR = true>
 PSG_DEV void slv_body(const KArgs& a) {
   __shared__ BlockCounters bc;
@@ -79,14 +78,10 @@ PSG_DEV void slv_body(const KArgs& a) {
 
   InstanceQueue<W, 0, W == 1 ? PSG_QUEUE_CHUNK_LANE : 0> Q;  // dynamic instance distribution (psg_device.hpp)
   for (uint64_t i = Q.take(a); i != Q.kDone; i = Q.take(a)) {
-    const uint64_t inst = a.ids ? a.ids[i] : a.inst_begin + i;
-    Sched<W, XHO> sc;
-    sc.setup(a, inst, g.pid, g.valid);
-    CrashSets<W> cs;  // per-instance crash rounds (no per-round exchange for W > 1)
-    if (sc.crash_on) cs.prep(g, crl, sc.crash_round);
-    sc.prep_good(0, g.lane, a.R);
-    int32_t x0 = 0;
-    if (g.valid) x0 = a.init ? init_x(a, i, inst, g.pid) : sc.init_value(g.pid, PSG_ALG_SLV);
+    Inst<W, XHO> in;
+    in.begin(g, a, i, crl);
+    Sched<W, XHO>& sc = in.sc;
+    const int32_t x0 = in.x0(g, a, i, PSG_ALG_SLV);
     X0Set<W> X0;
     X0.build(g, x0tab[grp], x0);
     // SlvProcess state after init(io) (ShortLastVoting.scala:15-31)
@@ -124,7 +119,7 @@ PSG_DEV void slv_body(const KArgs& a) {
         Mask<W> goodS;
         const bool good = sc.good_round(k, g.lane, a.R, goodS);
         Mask<W> CB = mzero<W>(), CN = mzero<W>();
-        if (sc.crash_on) cs.sets(g, k, CB, CN);
+        if (sc.crash_on) in.cs.sets(g, k, CB, CN);
         // R1 reads only bit coord of HO(p), and only when the coordinator sends
         // (ShortLastVoting.scala:53): the other rounds' and silent R1s' draws are skipped
         const bool sent = RS == 1 && cAlive && mtest(g.ballot((fl & S_COMMIT) != 0u), c);
@@ -213,10 +208,10 @@ PSG_DEV void slv_body(const KArgs& a) {
       if constexpr (!SH::kFused) check(k + 1);
       if (tracing<SH, TR>(a)) trace(k + 1, n, true);
     }
-    finish_instance<W>(g, a, i, SH::kFused ? sh.ck : ck, SH::kFused ? SH::kSlots : 2, dec_val, dec_round, halt_round, x, &bc);
+    finish_instance<W>(g, a, i, hook_checks<SH>(sh, ck), hook_slots<SH>(kKAgreeChecks), dec_val, dec_round, halt_round, x, &bc);
   }
   __syncthreads();
-  counters_flush(&bc, a.counters, SH::kFused ? SH::kSlots : 2, a.R);
+  counters_flush(&bc, a.counters, hook_slots<SH>(kKAgreeChecks), a.R);
 }
 
 #ifndef PSG_SLV_WPE
@@ -231,10 +226,9 @@ slv_kernel(KArgs a) {
 #ifndef PSG_FUSED_MODULE  // host launchers (not part of a fused Spec module)
 template <int W>
 static hipError_t launch_w(const KArgs& a, int grid, hipStream_t s) {
-  if (a.ho_in) hipLaunchKernelGGL((slv_kernel<W, true>), dim3(grid), dim3(Geometry<W>::kThreads), 0, s, a);
-  else if (a.trace) hipLaunchKernelGGL((slv_kernel<W, false>), dim3(grid), dim3(Geometry<W>::kThreads), 0, s, a);
-  else hipLaunchKernelGGL((slv_kernel<W, false, NoHook, false>), dim3(grid), dim3(Geometry<W>::kThreads), 0, s, a);
-  return hipGetLastError();
+  if (a.ho_in) return launch_grp<W>(slv_kernel<W, true>, a, grid, s);
+  if (a.trace) return launch_grp<W>(slv_kernel<W, false>, a, grid, s);
+  return launch_grp<W>(slv_kernel<W, false, NoHook, false>, a, grid, s);
 }
 
 hipError_t launch_slv(const KArgs& a, int W, int grid, hipStream_t s) {
