@@ -733,6 +733,26 @@ struct Grp {
     for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
     return v;
   }
+  // Inclusive prefix sums of a per-lane 64-bit value in lane order, in registers (the DPP steps
+  // of wave_sum32 with an add-with-carry pair per step; no LDS round trips): lane 63 holds the
+  // wave's sum. Call from converged control flow.
+  PSG_DEV static uint64_t wave_scan_sum64(uint64_t v) {
+    uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
+    // (bound_ctrl on the row shifts: a lane without a source reads 0, so no `old` value is set up
+    // and the moves fold into the adds; the row broadcasts leave the masked-off rows unchanged)
+#define PSG_SUM64(C, R, BC)                                                                       \
+  {                                                                                               \
+    const uint32_t dl = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)lo, C, R, 0xF, BC);         \
+    const uint32_t dh = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)hi, C, R, 0xF, BC);         \
+    const uint32_t nl = lo + dl;                                                                  \
+    hi += dh + (nl < dl ? 1u : 0u);                                                               \
+    lo = nl;                                                                                      \
+  }
+    PSG_SUM64(0x111, 0xF, true) PSG_SUM64(0x112, 0xF, true) PSG_SUM64(0x114, 0xF, true) PSG_SUM64(0x118, 0xF, true)
+    PSG_SUM64(0x142, 0xA, false) PSG_SUM64(0x143, 0xC, false)
+#undef PSG_SUM64
+    return ((uint64_t)hi << 32) | lo;
+  }
   PSG_DEV int32_t wave_min32(int32_t v) const { return dpp_reduce32<false>(v); }
   PSG_DEV int32_t wave_max32(int32_t v) const { return dpp_reduce32<true>(v); }
   template <int OP>  // 0 min, 1 max, 2 sum, 3 or
@@ -1270,11 +1290,12 @@ struct StepTally {
 template <int W>
 PSG_DEV void finish_instance(Grp<W>& g, const KArgs& a, uint64_t i, const Checks& ck, int nchecks, int32_t dec_val,
                              int32_t dec_round, int32_t halt_round, int32_t main_x, BlockCounters* bc,
-                             StepTally* tally = nullptr, int32_t live_rounds = -1) {
+                             StepTally* tally = nullptr, int32_t live_rounds = -1, PhaseTimers* pt = nullptr) {
   const int n = a.n;
   const bool decided = dec_round >= 0;
   const uint64_t d = g.valid ? proc_digest(g.pid, dec_val, dec_round, halt_round, main_x) : 0ull;
   const uint64_t dig = g.sum64(d);
+  if (pt) pt->mark(7);  // profiling build: the digest and its sum (OTR's sub-mark of the finish)
   const int nd = mpopc(g.ballot(decided));
   // rounds in which this process took a step: up to and including its halting round
   const int32_t steps = g.valid ? (halt_round >= 0 ? halt_round + 1 : a.R) : 0;
@@ -1316,6 +1337,93 @@ PSG_DEV void finish_instance(Grp<W>& g, const KArgs& a, uint64_t i, const Checks
     }
   }
   if (!tally && g.lane == 0) atomicAdd(&bc->active, (unsigned long long)wave_steps);
+}
+
+// Running sums of a wave's instances for finish_instance_w1, three VGPRs, flushed once per wave
+// beside StepTally::flush instead of four LDS atomics per instance. The sums that are uniform per
+// instance ride in lanes of the per-lane ones, so they neither occupy scalar registers nor issue
+// on the scalar pipe.
+struct WaveTally {
+  static constexpr int kDecidedLane = PSG_MAX_CHECKS + 1;
+  uint64_t acc = 0;  // lane 63: sum of the instance digests; lane 0: sum of the instances' live rounds
+  uint32_t cnt = 0;  // lane s < PSG_MAX_CHECKS: instances in which slot s failed; lane kDecidedLane: decided processes
+  // dig_scan: Grp::wave_scan_sum64 of the per-process digests (lane 63: the instance's digest)
+  PSG_DEV void add(int lane, uint64_t dig_scan, const Checks& ck, int nd, int32_t live_rounds) {
+    acc += lane == 0 ? (uint64_t)(uint32_t)live_rounds : dig_scan;
+    cnt += lane == kDecidedLane ? (uint32_t)nd : (ck.failed_here() ? 1u : 0u);
+  }
+  // every lane of the wave, converged
+  PSG_DEV void flush(BlockCounters* bc, int nchecks) {
+    const int lane = threadIdx.x & 63;
+    if (lane < nchecks && cnt) atomicAdd(&bc->fail[lane], cnt);
+    if (lane == kDecidedLane) atomicAdd(&bc->decided, cnt);
+    if (lane == 63) atomicAdd(&bc->digest, (unsigned long long)acc);
+    if (lane == 0) atomicAdd(&bc->live, (unsigned long long)acc);
+  }
+};
+
+// finish_instance for W == 1 kernels that keep a StepTally and a WaveTally and know the
+// instance's live rounds: the same outputs, byte for byte.
+// - The digest sum is a DPP scan (Grp::wave_scan_sum64): the total stays in lane 63.
+// - The 24-byte psg_instance_summary leaves as one 8-byte store from three lanes under one
+//   predicate: lane 63 the digest (bytes 0-7), lane 0 bytes 8-15, lane 8 bytes 16-23. Lane s of
+//   ck.ffv holds first_fail[s] (s < 12), i.e. bytes 8-19 in lane order: lane 4q gathers its
+//   quad's four bytes (two quad_perm steps), lanes 12-15 take term_round | n_checks << 8 |
+//   n_decided << 16 from a uniform word (a DPP move under a row and bank mask), and a row_shl:4
+//   brings the next quad's dword beside lanes 0 and 8.
+// - Only the Termination histogram is still counted per instance (the store's lanes add 0, 0, 1
+//   to the one bin); the other counters go through the WaveTally.
+PSG_DEV void finish_instance_w1(Grp<1>& g, const KArgs& a, uint64_t i, const Checks& ck, int nchecks, int32_t dec_val,
+                                int32_t dec_round, int32_t halt_round, int32_t main_x, BlockCounters* bc,
+                                StepTally* tally, WaveTally* wt, int32_t live_rounds, PhaseTimers* pt = nullptr) {
+  static_assert(PSG_MAX_CHECKS == 12 && sizeof(psg_instance_summary) == 24, "summary record layout");
+  const int n = a.n;
+  const bool decided = dec_round >= 0;
+  const uint64_t d = g.valid ? proc_digest(g.pid, dec_val, dec_round, halt_round, main_x) : 0ull;
+  const uint64_t scan = Grp<1>::wave_scan_sum64(d);
+  if (pt) pt->mark(7);
+  const int nd = mpopc(g.ballot(decided));
+  tally->add(g.valid ? (halt_round >= 0 ? halt_round + 1 : a.R) : 0);
+  if (g.valid) {
+    const uint64_t off = i * (uint64_t)n + (uint64_t)g.pid;
+    if (a.out_decision) a.out_decision[off] = dec_val;
+    if (a.out_dround) a.out_dround[off] = decided ? (uint8_t)dec_round : (uint8_t)0xFF;
+    if (a.out_rec) {
+      psg_process_record r;
+      r.decision = dec_val;
+      r.decision_round = dec_round;
+      r.halt_round = halt_round;
+      r.final_x = main_x;
+      a.out_rec[off] = r;
+    }
+  }
+  uint32_t lane = (uint32_t)g.lane;
+#if defined(__HIP_DEVICE_COMPILE__)
+  // opaque copy: the lane tests and the store offset are formed here per instance, not hoisted
+  // out of the instance loop and kept live across every round (the kernel sits at its VGPR limit)
+  asm volatile("" : "+v"(lane));
+#endif
+  const uint32_t term = ck.term_round();
+  const uint32_t b = (uint32_t)ck.ffv & 0xFFu;
+  const uint32_t b2 = b | ((uint32_t)__builtin_amdgcn_update_dpp(0, (int)b, 0xB1, 0xF, 0xF, false) << 8);  // quad_perm:[1,0,3,2]
+  uint32_t w0 = b2 | ((uint32_t)__builtin_amdgcn_update_dpp(0, (int)b2, 0x4E, 0xF, 0xF, false) << 16);  // quad_perm:[2,3,0,1]
+  const uint32_t tail = vgpr_u32((term & 0xFFu) | (((uint32_t)nchecks & 0xFFu) << 8) | ((uint32_t)nd << 16));
+  w0 = (uint32_t)__builtin_amdgcn_update_dpp((int)w0, (int)tail, 0xE4, 0x1, 0x8, false);  // lanes 12-15 <- tail
+  const uint32_t w1 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)w0, 0x104, 0xF, 0xF, false);  // row_shl:4
+  const bool last = lane == 63u;
+  const uint32_t lo = last ? (uint32_t)scan : w0, hi = last ? (uint32_t)(scan >> 32) : w1;
+  // lanes 0, 8, 63 (byte offsets 8, 16, 0), as one bit test: a disjunction of lane compares
+  // compiles to nested exec regions
+  if ((0x8000000000000101ull >> lane) & 1ull) {
+    if (a.out_inst) {
+      uint8_t* o = reinterpret_cast<uint8_t*>(a.out_inst + i);
+      *reinterpret_cast<uint64_t*>(o + ((lane + 8u) & 24u)) = (uint64_t)lo | ((uint64_t)hi << 32);
+    }
+    // (the bin index in a VGPR: with a uniform address the compiler sums the three addends in a
+    // scalar loop over the active lanes first)
+    atomicAdd(&bc->hist[vgpr_u32(term == PSG_NEVER ? (uint32_t)a.R + 1u : term)], last ? 1u : 0u);
+  }
+  wt->add((int)lane, scan, ck, nd, live_rounds);
 }
 
 // Process state at check point c for the Spec-program interpreter
@@ -1471,6 +1579,30 @@ struct X0Set {
     }
     has_empty = g.any(x0 == kEmpty);
     lds_sync<W>();
+  }
+  // build() for W == 1 when the launch's value domain is {1..V}, V <= 64 (Sched::init_value):
+  // one compare and one ballot test the fixed window [1, 65) instead of the min / max chains.
+  // A hit gives bitmap mode with lo = 1: every use of lo (bm_in01, the round-0 holder slots
+  // (x - lo) & 63) holds for any lo with all values in [lo, lo + 64), and bmode is what build()
+  // gives, since a hit implies a spread below 64. The bitmap itself comes from LDS without an OR
+  // chain: slot v - 1 of the (zeroed) table is marked by the lanes holding v, lane b reads slot b,
+  // and one ballot of the marks is the word (a wave's LDS operations execute in order). Lanes
+  // past n (x0 = 0) are masked out of the test and mark slot 64 + lane, which nobody reads.
+  // A miss (host-supplied values outside the window) is build() unchanged.
+  PSG_DEV void build_window(Grp<W>& g, int32_t* lds, int32_t x0, int32_t V) {
+    static_assert(W == 1, "the window form is W == 1 only");
+    if (V > 64 || g.any((uint32_t)(x0 - 1) >= 64u)) {
+      build(g, lds, x0);
+      return;
+    }
+    tab = lds;
+    bmode = true;
+    has_empty = false;
+    lo = 1;
+    lds[g.lane] = 0;
+    lds[g.valid ? x0 - 1 : 64 + g.lane] = 1;
+    lds_sync<W>();
+    bm = __builtin_amdgcn_ballot_w64(lds[g.lane] != 0);
   }
   // Uniform: does every process selected by `sel` hold a value of the set?
   // Fast path: one ballot of "v is in neither of its two home slots"; the probe

@@ -176,6 +176,41 @@ PSG_DEV void otr_check(Grp<W>& g, OtrLds<W>& L, const X0Set<W>& X0, Checks& ck, 
                              ox, irr01);
 }
 
+// Check point 0 for W == 1, from the state after init(io) (Otr.scala:15-26): no process has
+// decided and every x is an initial value. Each line is otr_check_general's with dec01 = 0 on
+// every lane and has_old = false: D is empty, so anyD = false and term = (D == full) is false
+// (n >= 1); the witness word is ox for OTR and 0 for OTR2, and where ox is set (a value outside
+// its two home slots of the hash table) the exact arm finds keep = all_in(x) true, as every x is
+// in the set built from these very values; validity and same range over the empty D and irrev
+// needs has_old, so all four hold, and condv = true. Hence
+//   OTR:  Invariant0 = (!anyD || e0) && keep holds, Invariant1 = e1 = (cnt == n), Invariant2 =
+//         term && d0in is false, Safety holds by Invariant0;
+//   OTR2: Invariant0 = term || e0 = (cnt > 2n/3), Invariant1 = (cnt == n), Invariant2 = same
+//         holds, Safety holds by Invariant2;
+//   Agreement, Validity, Integrity (!anyD) and Irrevocability hold, Termination does not.
+// cnt is otr_check_general's vote_count with anyD = false: against process 0's x for OTR,
+// against the majority candidate for OTR2. The fail word is a 32-bit scalar integer formed from
+// sign bits behind opaque copies, as in otr_check_general's no-witness arm.
+template <bool V2>
+PSG_DEV void otr_check_initial(Grp<1>& g, Checks& ck, int n, int32_t x, uint32_t valid01) {
+  const int32_t ref = V2 ? majority_candidate<1>(g, x) : readlane32(x, 0);
+  const int cnt = mpopc(g.ballot((valid01 & eq01(x, ref)) != 0u));
+  const uint32_t ne = opaque_uniform((uint32_t)(cnt - n)) >> 31;  // cnt != n (cnt <= n always)
+  uint32_t fb = ne << 2;
+  if constexpr (V2) fb |= (opaque_uniform((uint32_t)(cnt - (2 * n) / 3 - 1)) >> 31) << 1;  // cnt <= 2n/3
+  else fb |= 1u << 3;
+  ck.record(fb, false, 0, g.lane);
+}
+
+// The W == 1 forms of the per-instance setup and finish, each behind a bit for A/B builds
+// (-DPSG_OTR_SF=mask): 1 X0Set::build_window, 2 otr_check_initial, 4 finish_instance_w1
+// with the WaveTally. W > 1 keeps the general forms.
+#ifndef PSG_OTR_SF
+#define PSG_OTR_SF 7
+#endif
+template <int W>
+PSG_DEV constexpr bool kSF(int bit) { return W == 1 && (PSG_OTR_SF & bit) != 0; }
+
 // Kernel body; SH: the Spec hook (NoHook in psg_device.hpp). TR = false: the launch has no
 // Spec-program trace (a.trace == nullptr), known at compile time.
 template <int W, bool V2, bool XHO, class SH = NoHook, bool TR = true>
@@ -198,10 +233,13 @@ PSG_DEV void otr_body(const KArgs& a) {
   const uint32_t valid01 = g.valid ? 1u : 0u;
   const int32_t ckthr = W == 1 ? otr_check_thresholds<V2>(n, g.lane) : 0;  // (W > 1: unused)
 
-  PhaseTimers pt;  // profiling builds only: t0 setup, t1 active round, t2 frozen round, t3 finish
+  // profiling builds only: t1 active round, t2 frozen round; the setup is t4 queue take, t5 begin +
+  // initial value, t6 X0 set, t0 check point 0; the finish t7 digest and its sum, t3 the rest
+  PhaseTimers pt;
   pt.start();
   InstanceQueue<W, 0, W == 1 ? PSG_QUEUE_CHUNK_LANE : 0> Q;  // dynamic instance distribution (psg_device.hpp)
   StepTally tally;     // per-lane process-round steps, reduced once per wave
+  WaveTally wtally;    // W == 1: the other counters' sums, flushed once per wave
   // Host-supplied initial values are loaded one instance ahead: the next row's load is
   // issued when an instance starts and consumed when the next one does, so its latency
   // overlaps the current instance's rounds instead of stalling its setup.
@@ -216,13 +254,17 @@ PSG_DEV void otr_body(const KArgs& a) {
     const int32_t x0host = x0next;
     inext = Q.take(a);
     x0next = load_x0(inext);
+    pt.mark(4);
     Inst<W, XHO> in;
     in.begin(g, a, i, crl);
     Sched<W, XHO>& sc = in.sc;
     int32_t x0 = 0;
     if (g.valid) x0 = a.init ? x0host : sc.init_value(g.pid, PSG_ALG_OTR);
+    pt.mark(5);
     X0Set<W> X0;
-    X0.build(g, x0tab[grp], x0);
+    if constexpr (kSF<W>(1)) X0.build_window(g, x0tab[grp], x0, a.V);
+    else X0.build(g, x0tab[grp], x0);
+    pt.mark(6);
     // OtrProcess state after init(io) (Otr.scala:15-26); flags are 0/1 lane words
     int32_t x = x0, decision = -1, after = a.param;
     uint32_t od, ox;  // memoized X0 probes of decision / x (otr_check)
@@ -232,7 +274,10 @@ PSG_DEV void otr_body(const KArgs& a) {
     Checks ck;
     ck.reset();
     typename SH::template State<W> sh(g, grp, n);  // fused Spec evaluation state (NoHook: empty)
-    if constexpr (!SH::kFused) otr_check<W, V2>(g, L, X0, ck, 0, false, n, full, x, dec01, decision, 0u, -1, valid01, od, ox, ckthr);
+    if constexpr (!SH::kFused) {
+      if constexpr (kSF<W>(2)) otr_check_initial<V2>(g, ck, n, x, valid01);
+      else otr_check<W, V2>(g, L, X0, ck, 0, false, n, full, x, dec01, decision, 0u, -1, valid01, od, ox, ckthr);
+    }
     // OTR2's decision is an Option (PSG_NONE32 when empty)
     auto trace = [&](int c, int32_t hs, bool frozen = false) {
       emit_state<W, SH>(sh, g, a, i, c, x, (int32_t)dec01, V2 && !dec01 ? PSG_NONE32 : decision, 0, 0, 0, 0, 0, hs,
@@ -245,6 +290,7 @@ PSG_DEV void otr_body(const KArgs& a) {
     const bool hs_needed = SH::kFused ? ((SH::kFields >> PSG_FIELD_HOSIZE) & 1u) != 0u
                                       : (TR && a.trace != nullptr && ((a.trace_fields >> PSG_FIELD_HOSIZE) & 1u));
     int32_t live_rounds = 0;  // rounds in which some process took a step
+    bool good_read = false;   // (event build only)
     int kf = a.R;             // first round in which every process had halted (the state is final)
     for (int k = 0; k < a.R; ++k) {
       const uint32_t old01 = dec01;
@@ -274,6 +320,9 @@ PSG_DEV void otr_body(const KArgs& a) {
         if (!settled) {
         Mask<W> goodS;
         const bool good = sc.good_round(k, g.lane, a.R, goodS);
+        pt.add(4, good ? 1u : 0u);  // event build: good rounds executed unsettled
+        pt.add(5, good && !good_read ? 1u : 0u);  // ... the first of them in an instance
+        if (PSG_PHASE_TIMERS == 2) good_read = good_read || good;
         Mask<W> CB = mzero<W>(), CN = mzero<W>();
         if (sc.crash_on) in.cs.sets(g, k, CB, CN);
         // mailbox: broadcast(x) from every alive sender in HO(p)
@@ -364,12 +413,18 @@ PSG_DEV void otr_body(const KArgs& a) {
       if (tracing_on) trace(k + 1, n, true);
       pt.mark(2);
     }
-    finish_instance<W>(g, a, i, hook_checks<SH>(sh, ck), hook_slots<SH>(kOtrChecks), dec_val, dec_round, halt_round, x, &bc,
-                       &tally, live_rounds);
+    pt.add(6, 1u);  // event build: instances
+    if constexpr (kSF<W>(4))
+      finish_instance_w1(g, a, i, hook_checks<SH>(sh, ck), hook_slots<SH>(kOtrChecks), dec_val, dec_round, halt_round, x,
+                         &bc, &tally, &wtally, live_rounds, &pt);
+    else
+      finish_instance<W>(g, a, i, hook_checks<SH>(sh, ck), hook_slots<SH>(kOtrChecks), dec_val, dec_round, halt_round, x,
+                         &bc, &tally, live_rounds, &pt);
     pt.mark(3);
   }
   pt.flush(a.counters, threadIdx.x & 63);
   tally.flush(&bc);
+  if constexpr (kSF<W>(4)) wtally.flush(&bc, hook_slots<SH>(kOtrChecks));
   __syncthreads();
   counters_flush(&bc, a.counters, hook_slots<SH>(kOtrChecks), a.R);
 }
