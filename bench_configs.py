@@ -6,6 +6,7 @@
       the same sweep over f
   C5  BenOr n=128, 64 rounds, |HO(p)| > n/2; termination-round histogram all-reduced
   W2  second-wave algorithms: OTR2, ShortLastVoting, KSetEarlyStopping, EpsilonConsensus
+  W3  TwoPhaseCommit n=64, 1e7 instances, 3 rounds (one phase)
 
 One process per GPU (torchrun), weak scaling, RCCL all-reduce of the summaries.
 Prints one JSON line per configuration (rank 0). Algorithmic bytes per
@@ -51,6 +52,8 @@ def configs(scale):
     out.append(("W2_slv_n64", psync.ShortLastVoting(), 64, int(12_500_000 * s), {}, 40))
     out.append(("W2_kset_es_n256_t64_k2", psync.KSetEarlyStopping(64, 2), 256, int(1_000_000 * s), {}, 32))
     out.append(("W2_epsilon_n64_f5", psync.EpsilonConsensus(5, 1e-6), 64, int(1_000_000 * s), {}, 66))
+    # atomic commitment: TwoPhaseCommit, one phase (R = 3); (decision 4 B + vote 1 B) x 2 + init 4
+    out.append(("W3_tpc_n64", psync.TwoPhaseCommit(), 64, int(10_000_000 * s), {}, 14))
     # generic Spec programs: the reference Specs compiled from the Formula
     # DSL and interpreted on the device over the traced states (psg_run_batch_spec)
     from round_amd import formula

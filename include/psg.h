@@ -64,7 +64,9 @@ enum psg_alg {
   PSG_ALG_OTR2 = 6,        /* example.OTR2               example/Otr2.scala:9-104 */
   PSG_ALG_SLV = 7,         /* example.ShortLastVoting    example/ShortLastVoting.scala:13-119 */
   PSG_ALG_KSET_ES = 8,     /* example.KSetEarlyStopping  example/KSetEarlyStopping.scala:9-57 */
-  PSG_ALG_EPSILON = 9      /* example.EpsilonConsensus   example/Epsilon.scala:16-83 (Double values) */
+  PSG_ALG_EPSILON = 9,     /* example.EpsilonConsensus   example/Epsilon.scala:16-83 (Double values) */
+  /* atomic commitment (not consensus): a fixed coordinator, an Option[Boolean] decision */
+  PSG_ALG_TPC = 10         /* example.TwoPhaseCommit     example/TwoPhaseCommit.scala:15-108 */
 };
 
 /* Which element of a Scala immutable.Map is "first" (LastVoting maxBy ties,
@@ -112,9 +114,12 @@ typedef struct psg_config {
   int32_t rounds;       /* R rounds executed per instance, 1..PSG_MAX_ROUNDS */
   uint64_t seed;
   int32_t value_range;  /* synthetic init values uniform in {1..value_range} (BenOr: {false,true};
-                           EpsilonConsensus: Double uniform in [0,1) like Random.nextDouble, unused) */
+                           EpsilonConsensus: Double uniform in [0,1) like Random.nextDouble, unused;
+                           TwoPhaseCommit: canCommit = (value != 1), i.e. P(no vote) = 1 / value_range) */
   int32_t param;        /* OTR/OTR2 afterDecision (Otr.scala:89, default 2); FloodMin f (FloodMin.scala:27);
-                           KSet k (KSetAgreement.scala:56); KSetEarlyStopping t; others unused */
+                           KSet k (KSetAgreement.scala:56); KSetEarlyStopping t; TwoPhaseCommit coord (the
+                           io.coord of every process, TwoPhaseCommit.scala:24, 87; 0 <= coord < n, default 0);
+                           others unused */
   int32_t tiebreak;     /* enum psg_tiebreak */
   int32_t device;       /* HIP device ordinal (n_devices == 0) */
   int32_t variant;      /* 0 = reference algorithm; 1 = test mutation */
@@ -163,10 +168,12 @@ typedef struct psg_instance_summary {
  * and final_x hold fold32(bits) = low ^ high word of the IEEE-754 bits; the
  * values themselves come from the _f64 entry points below. */
 typedef struct psg_process_record {
-  int32_t decision;       /* value passed to ConsensusIO.decide (BenOr: 0/1); 0 if none */
-  int32_t decision_round; /* round k (0-based) of the first decide callback, -1 if none */
+  int32_t decision;       /* value passed to ConsensusIO.decide (BenOr: 0/1); 0 if none. TwoPhaseCommit: 1 / 0
+                             for TpcIO.decide(Some(true / false)), PSG_NONE32 for decide(None) and for no callback */
+  int32_t decision_round; /* round k (0-based) of the first decide callback, -1 if none (TwoPhaseCommit:
+                             decide(None), "coordinator suspected", is not a decision: -1) */
   int32_t halt_round;     /* round k whose update called exitAtEndOfRound, -1 if never */
-  int32_t final_x;        /* final main variable (OTR/LV/FloodMin x, BenOr x, KSet pick(t)) */
+  int32_t final_x;        /* final main variable (OTR/LV/FloodMin x, BenOr x, KSet pick(t), TwoPhaseCommit vote) */
 } psg_process_record;
 
 /* ---------------------------------------------------------------------------
@@ -186,13 +193,17 @@ typedef struct psg_process_record {
 
 /* Process-state fields visible to a Spec (the variables the reference specs read). */
 enum psg_field {
-  PSG_FIELD_X = 0,        /* x (OTR/LV/FloodMin/SLV), est (KSetEarlyStopping), pick(t) (KSet), x (BenOr 0/1) */
-  PSG_FIELD_DECIDED = 1,  /* decided flag (ghost for algorithms without one: decide callback fired) */
-  PSG_FIELD_DECISION = 2, /* decision (OTR2: Option, PSG_NONE32 when empty) */
+  PSG_FIELD_X = 0,        /* x (OTR/LV/FloodMin/SLV), est (KSetEarlyStopping), pick(t) (KSet), x (BenOr 0/1),
+                             vote (TwoPhaseCommit 0/1) */
+  PSG_FIELD_DECIDED = 1,  /* decided flag (ghost for algorithms without one: decide callback fired;
+                             TwoPhaseCommit: decision.isDefined) */
+  PSG_FIELD_DECISION = 2, /* decision (OTR2: Option, PSG_NONE32 when empty; TwoPhaseCommit: Option[Boolean],
+                             PSG_NONE32 / 0 / 1) */
   PSG_FIELD_TS = 3,       /* LastVoting / ShortLastVoting ts */
   PSG_FIELD_READY = 4,    /* LastVoting ready */
   PSG_FIELD_COMMIT = 5,   /* LastVoting / ShortLastVoting commit */
-  PSG_FIELD_VOTE = 6,     /* LastVoting / SLV vote; BenOr vote (Option[Boolean], PSG_NONE32 when empty) */
+  PSG_FIELD_VOTE = 6,     /* LastVoting / SLV vote; BenOr vote (Option[Boolean], PSG_NONE32 when empty);
+                             TwoPhaseCommit vote (0/1) */
   PSG_FIELD_CANDECIDE = 7,/* BenOr canDecide */
   PSG_FIELD_HOSIZE = 8,   /* |mailbox| of the round just executed (n if the process took no step) */
   PSG_NFIELDS = 9

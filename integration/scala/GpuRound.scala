@@ -66,7 +66,10 @@ object GpuRound {
   val registry: Map[String, Int] = Map(
     "example.OTR" -> 1, "example.LastVoting" -> 2, "example.FloodMin" -> 3,
     "example.KSetAgreement" -> 4, "example.BenOr" -> 5, "example.OTR2" -> 6,
-    "example.ShortLastVoting" -> 7, "example.KSetEarlyStopping" -> 8, "example.EpsilonConsensus" -> 9)
+    "example.ShortLastVoting" -> 7, "example.KSetEarlyStopping" -> 8, "example.EpsilonConsensus" -> 9,
+    // TpcIO (coord, canCommit, decide(Option[Boolean])) is not a ConsensusIO: inputs are the votes 0 / 1,
+    // psg_config.param the coordinator, decisions 1 / 0 / PSG_NONE32 (INTEGRATION.md)
+    "example.TwoPhaseCommit" -> 10)
   private val realValued = Set(9)
 
   def algId(alg: Algorithm[_, _]): Int =

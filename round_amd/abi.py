@@ -16,6 +16,7 @@ PSG_ALG_OTR2 = 6
 PSG_ALG_SLV = 7
 PSG_ALG_KSET_ES = 8
 PSG_ALG_EPSILON = 9
+PSG_ALG_TPC = 10
 
 PSG_TIE_CHAMP = 0
 PSG_TIE_MIN_PID = 1
@@ -45,6 +46,7 @@ CLASS_TO_ALG = {
     "example.ShortLastVoting": PSG_ALG_SLV,
     "example.KSetEarlyStopping": PSG_ALG_KSET_ES,
     "example.EpsilonConsensus": PSG_ALG_EPSILON,
+    "example.TwoPhaseCommit": PSG_ALG_TPC,
 }
 
 # Check-slot names per algorithm (psg_check_name). Slot 0 of OTR/LV/BenOr is
@@ -62,6 +64,7 @@ CHECK_NAMES = {
     PSG_ALG_SLV: ["KAgreement", "KValidity"],
     PSG_ALG_KSET_ES: ["KAgreement", "KValidity"],
     PSG_ALG_EPSILON: ["EpsAgreement", "EpsValidity", "SafetyPredicate"],
+    PSG_ALG_TPC: ["Safety", "Invariant0", "UniformAgreement", "Validity"],
 }
 # Slots whose falsity is a violation (invariant slots are informational: an
 # individual invariant of a sequence legitimately fails before/after its phase;
@@ -77,6 +80,7 @@ VIOLATION_SLOTS = {
     PSG_ALG_SLV: [0, 1],
     PSG_ALG_KSET_ES: [0, 1],
     PSG_ALG_EPSILON: [0, 1],
+    PSG_ALG_TPC: [0, 2, 3],
 }
 
 

@@ -21,7 +21,7 @@ the device, keep the ones that get closest to a violation.
     predicate in at least `live_rounds` rounds; the target is non-termination
     within R rounds (term_round == never).
   * fault models: general omission (OTR, OTR2, LastVoting, ShortLastVoting,
-    BenOr, EpsilonConsensus) or crash-stop with at most f crashes (FloodMin,
+    BenOr, EpsilonConsensus, TwoPhaseCommit) or crash-stop with at most f crashes (FloodMin,
     KSetAgreement, KSetEarlyStopping — their runners' fault model).
 Every counterexample is shrunk (batched delta debugging: all candidate
 simplifications of one step run as one GPU batch) and can be written to a
@@ -108,6 +108,8 @@ def default_model(alg: psync.Algorithm, n: int) -> Model:
         return Model("crash", fmax=alg.param - 1)
     if a == abi.PSG_ALG_KSET_ES:
         return Model("crash", fmax=alg.param)
+    if a == abi.PSG_ALG_TPC:
+        return Model("omission")  # (its livenessPredicate: schedules.fixed_coord_live; no liveness search)
     raise ValueError(f"no fault model for {alg.class_name}")
 
 
@@ -117,6 +119,8 @@ def default_init(alg: psync.Algorithm, rng, I: int, n: int, values: int) -> np.n
         return rng.random((I, n))
     if alg.alg_id == abi.PSG_ALG_BENOR:
         return rng.integers(0, 2, (I, n), dtype=np.int32)
+    if alg.alg_id == abi.PSG_ALG_TPC:  # votes io.canCommit, mostly yes: no w.p. 1 / values
+        return (rng.integers(0, max(values, 1), (I, n)) != 0).astype(np.int32)
     return rng.integers(1, values + 1, (I, n), dtype=np.int32)  # nonzero (LastVoting.scala:134)
 
 

@@ -30,7 +30,9 @@ __global__ void gen_init_kernel(uint64_t inst_begin, uint64_t count, int n, int 
     const uint64_t i = e / (uint64_t)n;
     const int p = (int)(e - i * (uint64_t)n);
     const uint64_t w = rword(seed, inst_begin + i, ROUND_INIT, (uint32_t)p, 0);
-    out[e] = alg == PSG_ALG_BENOR ? (int32_t)((uint32_t)w & 1u) : 1 + (int32_t)mulhi32((uint32_t)w, (uint32_t)V);
+    out[e] = alg == PSG_ALG_BENOR ? (int32_t)((uint32_t)w & 1u)
+             : alg == PSG_ALG_TPC ? tpc_vote((uint32_t)w, (uint32_t)V)
+                                  : 1 + (int32_t)mulhi32((uint32_t)w, (uint32_t)V);
   }
 }
 
@@ -141,12 +143,14 @@ static const char* const k_names_lv[] = {"Safety", "Invariant0", "Invariant1", "
 static const char* const k_names_benor[] = {"Safety", "Invariant0", "Agreement", "Irrevocability", "SafetyPredicate"};
 static const char* const k_names_k[] = {"KAgreement", "KValidity"};
 static const char* const k_names_eps[] = {"EpsAgreement", "EpsValidity", "SafetyPredicate"};
+static const char* const k_names_tpc[] = {"Safety", "Invariant0", "UniformAgreement", "Validity"};
 // the kernels record and flush exactly the named slots (psg_device.hpp)
 static_assert(std::size(k_names_otr) == kOtrChecks, "k_names_otr and kOtrChecks disagree");
 static_assert(std::size(k_names_lv) == kLvChecks, "k_names_lv and kLvChecks disagree");
 static_assert(std::size(k_names_benor) == kBenOrChecks, "k_names_benor and kBenOrChecks disagree");
 static_assert(std::size(k_names_k) == kKAgreeChecks, "k_names_k and kKAgreeChecks disagree");
 static_assert(std::size(k_names_eps) == kEpsilonChecks, "k_names_eps and kEpsilonChecks disagree");
+static_assert(std::size(k_names_tpc) == kTpcChecks, "k_names_tpc and kTpcChecks disagree");
 
 struct CheckNames {
   const char* const* name;
@@ -246,10 +250,23 @@ static const AlgRow k_algs[] = {
        return c.param < 1 || !(c.real_param > 0.0) ? "EpsilonConsensus needs f >= 1 and epsilon > 0" : nullptr;
      },
      launch_epsilon, epsilon_kernel_ptr},
+    {"example.TwoPhaseCommit", k_names_tpc,
+     [](psg_config& c, int n) {  // one phase; votes no w.p. 1/(2n): both outcomes stay common at any n
+       c.param = 0;  // coord (TpcRunner: ProcessID(0), TwoPhaseCommit.scala:130)
+       c.rounds = 3;
+       c.value_range = 2 * n;
+       c.sched.drop_log2 = 6;
+       c.sched.good_p32 = 0;
+     },
+     [](const psg_config& c) {
+       if (const char* m = need_value_range(c)) return m;
+       return c.param < 0 || c.param >= c.n ? "TwoPhaseCommit needs 0 <= coord < n" : nullptr;
+     },
+     launch_tpc, tpc_kernel_ptr},
 };
 
 constexpr int k_alg_rows = (int)(sizeof(k_algs) / sizeof(k_algs[0]));
-static_assert(k_alg_rows == PSG_ALG_EPSILON + 1, "one row per PSG_ALG_*, in the enum's order");
+static_assert(k_alg_rows == PSG_ALG_TPC + 1, "one row per PSG_ALG_*, in the enum's order");
 
 // The row of an algorithm id; null: unknown algorithm.
 static const AlgRow* alg_row(int alg) { return alg > 0 && alg < k_alg_rows ? &k_algs[alg] : nullptr; }
@@ -1323,7 +1340,7 @@ static PopArgs pop_args(const psg_ctx* c, const psg_population_params* p, uint64
   for (int j = 0; j < 4; ++j) a.keep[j] = p->keep_p256[j];
   a.V = p->value_range;
   a.redraw = p->redraw_p256;
-  a.benor = c->cfg.alg == PSG_ALG_BENOR;
+  a.init_kind = c->cfg.alg == PSG_ALG_BENOR ? POP_INIT_COIN : c->cfg.alg == PSG_ALG_TPC ? POP_INIT_VOTE : POP_INIT_VALUE;
   return a;
 }
 

@@ -121,8 +121,10 @@ struct PopArgs {
   uint32_t keep[4];
   int32_t V;
   uint32_t redraw;
-  int benor;
+  int init_kind;  // POP_INIT_*
 };
+// a population's initial values: {1..V}; BenOr's {0, 1} coin bit; TwoPhaseCommit's vote (tpc_vote)
+enum { POP_INIT_VALUE = 0, POP_INIT_COIN = 1, POP_INIT_VOTE = 2 };
 
 #ifndef PSG_PHASE_TIMERS
 #define PSG_PHASE_TIMERS 0
@@ -283,6 +285,10 @@ struct WordStream {
 };
 
 PSG_DEV uint32_t mulhi32(uint32_t a, uint32_t b) { return __umulhi(a, b); }
+
+// TwoPhaseCommit's seeded io.canCommit from the process's init word: the value every other
+// algorithm draws, 1 + mulhi32(w, V) in {1..V}, votes no iff it is 1, so P(no vote) = 1 / V
+PSG_DEV int32_t tpc_vote(uint32_t w, uint32_t V) { return mulhi32(w, V) != 0u ? 1 : 0; }
 
 // java.util.Random(s).nextBoolean(): BenOr coin (example/BenOr.scala:77)
 PSG_DEV bool java_first_boolean(uint64_t s) {
@@ -977,6 +983,7 @@ struct Sched {
   PSG_DEV int32_t init_value(int pid, int alg) const {
     const uint64_t w = rword(seed, inst, ROUND_INIT, (uint32_t)pid, 0);
     if (alg == PSG_ALG_BENOR) return (int32_t)((uint32_t)w & 1u);
+    if (alg == PSG_ALG_TPC) return tpc_vote((uint32_t)w, (uint32_t)V);
     return 1 + (int32_t)mulhi32((uint32_t)w, (uint32_t)V);
   }
 
@@ -1472,6 +1479,7 @@ constexpr int kLvChecks = 7;       // LastVoting
 constexpr int kBenOrChecks = 5;    // BenOr
 constexpr int kKAgreeChecks = 2;   // FloodMin, KSet, ShortLastVoting, KSetEarlyStopping
 constexpr int kEpsilonChecks = 3;  // EpsilonConsensus
+constexpr int kTpcChecks = 4;      // TwoPhaseCommit
 // The check slots and the Checks a kernel with hook SH reports: the fused Spec's, else the built-in ones.
 template <class SH>
 PSG_DEV constexpr int hook_slots(int builtin) { return SH::kFused ? SH::kSlots : builtin; }

@@ -1215,6 +1215,7 @@ bool fused_kernel(int alg, std::string& src, std::string& body, std::string& tar
     case PSG_ALG_BENOR: src = "psg_benor.hip"; body = "benor_body"; break;
     case PSG_ALG_SLV: src = "psg_slv.hip"; body = "slv_body"; break;
     case PSG_ALG_KSET_ES: src = "psg_kset_es.hip"; body = "kset_es_body"; break;
+    case PSG_ALG_TPC: src = "psg_tpc.hip"; body = "tpc_body"; break;
     default: return false;
   }
   targs_w_prefix.clear();

@@ -53,6 +53,7 @@ ALG_FIELDS = {
     abi.PSG_ALG_BENOR: {FIELD_X, FIELD_DECIDED, FIELD_DECISION, FIELD_CANDECIDE, FIELD_VOTE, FIELD_HOSIZE},
     abi.PSG_ALG_SLV: {FIELD_X, FIELD_DECIDED, FIELD_DECISION, FIELD_TS, FIELD_COMMIT, FIELD_VOTE, FIELD_HOSIZE},
     abi.PSG_ALG_KSET_ES: {FIELD_X, FIELD_DECIDED, FIELD_DECISION, FIELD_HOSIZE},
+    abi.PSG_ALG_TPC: {FIELD_X, FIELD_DECIDED, FIELD_DECISION, FIELD_VOTE, FIELD_HOSIZE},
 }
 
 
@@ -679,11 +680,27 @@ def benor_spec() -> Spec:
     return Spec([inv0], rinv, props, safety_predicate=P.forall(lambda p: p.HO.size > n // 2), phase_length=2)
 
 
+def tpc_spec() -> Spec:
+    """example/TwoPhaseCommit.scala:93-105 (decision: Option[Boolean], vote: Boolean). The source's
+    "Uniform Agreement" is the slot UniformAgreement; its Termination is a comment (:106), here the
+    check point where every decision is defined."""
+    validity = P.forall(lambda p: (p.decision == Some(true)).implies(P.forall(lambda q: q.vote)))
+    agreement = P.forall(lambda p: P.forall(lambda q: (p.decision.isDefined & q.decision.isDefined).implies(
+        p.decision == q.decision)))
+    props = [
+        ("UniformAgreement", agreement),
+        ("Validity", validity),
+        ("Termination", P.forall(lambda p: p.decision.isDefined)),
+    ]
+    return Spec([validity & agreement], properties=props, phase_length=3)
+
+
 REFERENCE_SPECS = {
     abi.PSG_ALG_OTR: otr_spec,
     abi.PSG_ALG_OTR2: otr2_spec,
     abi.PSG_ALG_LAST_VOTING: lv_spec,
     abi.PSG_ALG_BENOR: benor_spec,
+    abi.PSG_ALG_TPC: tpc_spec,
 }
 
 
@@ -698,7 +715,8 @@ REFERENCE_SPECS = {
 
 # algorithms whose round kernel a fused module instantiates with the Spec as its check hook
 FUSED_KERNELS = frozenset({abi.PSG_ALG_OTR, abi.PSG_ALG_OTR2, abi.PSG_ALG_LAST_VOTING, abi.PSG_ALG_FLOODMIN,
-                           abi.PSG_ALG_KSET, abi.PSG_ALG_BENOR, abi.PSG_ALG_SLV, abi.PSG_ALG_KSET_ES})
+                           abi.PSG_ALG_KSET, abi.PSG_ALG_BENOR, abi.PSG_ALG_SLV, abi.PSG_ALG_KSET_ES,
+                           abi.PSG_ALG_TPC})
 
 # Generator options, on only for A/B measurements (PSG_SPEC_OPTIONS, include/psg.h): the
 # symmetric-check-point lowering (spec::uniform) and the split foralls / hoisted conjuncts.

@@ -219,8 +219,31 @@ class EpsilonConsensus(Algorithm):
         return 12
 
 
+class TwoPhaseCommit(Algorithm):
+    """example.TwoPhaseCommit(rt, timeout) — example/TwoPhaseCommit.scala:81 (3-round phase, atomic
+    commitment). `coord` is the TpcIO.coord of every process (the Axiom "well-coordinated", :87);
+    inputs are the votes io.canCommit (0 / nonzero); a decision is Option[Boolean]: 1 / 0, and
+    PSG_NONE32 for decide(None), which is not a decision (decision_round -1)."""
+    class_name = "example.TwoPhaseCommit"
+    alg_id = abi.PSG_ALG_TPC
+    phase_length = 3
+
+    def __init__(self, coord=0, variant=0):
+        super().__init__(coord, variant)
+
+    def default_schedule(self, n):
+        return HOSchedule(drop_log2=6, good_round=0.0)
+
+    def default_rounds(self, n):
+        return 3
+
+    def default_value_range(self, n):
+        return 2 * n  # seeded votes: no w.p. 1 / value_range, so both outcomes stay common at any n
+
+
 ALGORITHMS = {c.class_name: c for c in (OTR, LastVoting, FloodMin, KSetAgreement, BenOr,
-                                          OTR2, ShortLastVoting, KSetEarlyStopping, EpsilonConsensus)}
+                                          OTR2, ShortLastVoting, KSetEarlyStopping, EpsilonConsensus,
+                                          TwoPhaseCommit)}
 
 
 def make_config(alg: Algorithm, n: int, rounds: Optional[int] = None, seed: int = 1,

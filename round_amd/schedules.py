@@ -16,6 +16,8 @@ Predicates restate the Specs' environment assumptions over given HO sets:
   * LastVoting `livenessPredicate`
     `P.exists(p => P.forall(q => p == coord && p.HO.contains(q) && p.HO.size > n/2))`
     (example/LastVoting.scala:20-22): the coordinator of the round hears everyone
+  * TwoPhaseCommit `livenessPredicate` (example/TwoPhaseCommit.scala:90-92): the fixed
+    coordinator hears everyone and everyone hears it
   * EpsilonConsensus: |HO(p)| >= n - f (the commented assert `mailbox.size >= n - f`,
     example/Epsilon.scala:57)
   * crash-stop with at most f crashes (FloodMin / KSet / KSetEarlyStopping runners)
@@ -91,6 +93,22 @@ def coord_hears_all(ho: np.ndarray, n: int, phase: int = 4) -> np.ndarray:
     for k in range(R):
         c = (k // phase) % n
         out[:, k] = (ho[:, k, c, :] == fm).all(-1)
+    return out
+
+
+def fixed_coord_live(ho: np.ndarray, n: int, coord: int = 0) -> np.ndarray:
+    """TwoPhaseCommit livenessPredicate `P.exists(p => P.forall(q => p == q.coord && p.HO.size == n
+    && (q.HO contains p)))` (example/TwoPhaseCommit.scala:90-92), split over the phase's rounds by
+    what each one reads: in slot 1 (k % 3 == 1) the coordinator hears all n processes, in slot 2
+    everyone hears the coordinator; slot 0 reads no HO set -> bool [I][R]."""
+    I, R = ho.shape[:2]
+    fm = full_mask(n)
+    out = np.ones((I, R), bool)
+    for k in range(R):
+        if k % 3 == 1:
+            out[:, k] = (ho[:, k, coord, :] == fm).all(-1)
+        elif k % 3 == 2:
+            out[:, k] = contains(ho[:, k], coord).all(-1)
     return out
 
 

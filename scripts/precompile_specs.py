@@ -33,6 +33,10 @@ def jobs():
     out.append(("lv_custom", abi.PSG_ALG_LAST_VOTING, False, None))
     out.append(("ref", abi.PSG_ALG_OTR, True, 64))
     out.append(("ref", abi.PSG_ALG_LAST_VOTING, True, 64))
+    # tests/test_gpu_tpc.py: TwoPhaseCommit's Spec native, and fused at W = 1 and W = 3
+    out.append(("ref", abi.PSG_ALG_TPC, False, None))
+    out.append(("ref", abi.PSG_ALG_TPC, True, 8))
+    out.append(("ref", abi.PSG_ALG_TPC, True, 130))
     # the Formula-text route (psg_spec_compile_native: the library's own generator + hiprtc),
     # tests/test_spec_native_text.py, tests/test_jni_shim.py and the G1 *_text rows
     for a, n in ((abi.PSG_ALG_OTR, 64), (abi.PSG_ALG_LAST_VOTING, 64), (abi.PSG_ALG_OTR2, 100),
