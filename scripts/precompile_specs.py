@@ -37,6 +37,9 @@ def jobs():
     out.append(("ref", abi.PSG_ALG_TPC, False, None))
     out.append(("ref", abi.PSG_ALG_TPC, True, 8))
     out.append(("ref", abi.PSG_ALG_TPC, True, 130))
+    # tests/test_gpu_rounds.py: the reference Spec plus a property over |HO(p)|, fused
+    out.append(("ref_ho", abi.PSG_ALG_OTR, True, 64))
+    out.append(("ref_ho", abi.PSG_ALG_LAST_VOTING, True, 64))
     # the Formula-text route (psg_spec_compile_native: the library's own generator + hiprtc),
     # tests/test_spec_native_text.py, tests/test_jni_shim.py and the G1 *_text rows
     for a, n in ((abi.PSG_ALG_OTR, 64), (abi.PSG_ALG_LAST_VOTING, 64), (abi.PSG_ALG_OTR2, 100),
@@ -54,6 +57,8 @@ def build(job):
         return os.path.basename(lib.spec_compile_native(F.to_text(F.REFERENCE_SPECS[alg]()), alg, fused, n).module_path)
     if kind in ("ref", "fusedbuild"):
         spec = F.REFERENCE_SPECS[alg]() if alg in F.REFERENCE_SPECS else spec_cases.uniform_agreement()
+    elif kind == "ref_ho":
+        spec = spec_cases.ref_with_ho_bound(alg)
     elif kind == "lv_custom":
         spec = spec_cases.lv_custom()
     else:

@@ -187,6 +187,14 @@ def term_shared_shapes():
     ])
 
 
+def ref_with_ho_bound(alg_id):
+    """The reference Spec of alg_id with one more property, over |HO(p)| (tests/test_gpu_rounds.py):
+    a program that reads the HOSIZE field, so the round kernels keep every round's mailbox size."""
+    spec = F.REFERENCE_SPECS[alg_id]()
+    spec.properties.append(("HoBound", F.lift(P.forall(lambda p: p.HO.size <= n))))
+    return spec
+
+
 # (id, algorithm, n, make_config kwargs, spec factory)
 CUSTOM = [
     ("fm-n12", psync.FloodMin(2), 12, dict(value_range=8, schedule=H(drop_log2=0, good_round=0.0, crash_fmax=3)),
