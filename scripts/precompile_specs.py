@@ -45,6 +45,10 @@ def jobs():
     for a, n in ((abi.PSG_ALG_OTR, 64), (abi.PSG_ALG_LAST_VOTING, 64), (abi.PSG_ALG_OTR2, 100),
                  (abi.PSG_ALG_BENOR, 128)):
         out.append(("text", a, True, n))
+    # tests/test_gpu_instantiations.py: every fused algorithm at W = 1..4
+    import test_gpu_instantiations as TI
+    for name, n in TI.fused_modules():
+        out.append(("inst:" + name, TI.ALG_ID[name], True, n))
     return sorted(set(out), key=str)
 
 
@@ -57,6 +61,9 @@ def build(job):
         return os.path.basename(lib.spec_compile_native(F.to_text(F.REFERENCE_SPECS[alg]()), alg, fused, n).module_path)
     if kind in ("ref", "fusedbuild"):
         spec = F.REFERENCE_SPECS[alg]() if alg in F.REFERENCE_SPECS else spec_cases.uniform_agreement()
+    elif kind.startswith("inst:"):
+        import test_gpu_instantiations as TI
+        spec = TI.spec_of(kind[5:])
     elif kind == "ref_ho":
         spec = spec_cases.ref_with_ho_bound(alg)
     elif kind == "lv_custom":
