@@ -66,7 +66,9 @@ enum psg_alg {
   PSG_ALG_KSET_ES = 8,     /* example.KSetEarlyStopping  example/KSetEarlyStopping.scala:9-57 */
   PSG_ALG_EPSILON = 9,     /* example.EpsilonConsensus   example/Epsilon.scala:16-83 (Double values) */
   /* atomic commitment (not consensus): a fixed coordinator, an Option[Boolean] decision */
-  PSG_ALG_TPC = 10         /* example.TwoPhaseCommit     example/TwoPhaseCommit.scala:15-108 */
+  PSG_ALG_TPC = 10,        /* example.TwoPhaseCommit     example/TwoPhaseCommit.scala:15-108 */
+  /* lattice agreement (neither consensus nor commitment): the state is a set, the update a join */
+  PSG_ALG_LATTICE = 11     /* example.LatticeAgreement   example/LatticeAgreement.scala:32-68 */
 };
 
 /* Which element of a Scala immutable.Map is "first" (LastVoting maxBy ties,
@@ -115,7 +117,9 @@ typedef struct psg_config {
   uint64_t seed;
   int32_t value_range;  /* synthetic init values uniform in {1..value_range} (BenOr: {false,true};
                            EpsilonConsensus: Double uniform in [0,1) like Random.nextDouble, unused;
-                           TwoPhaseCommit: canCommit = (value != 1), i.e. P(no vote) = 1 / value_range) */
+                           TwoPhaseCommit: canCommit = (value != 1), i.e. P(no vote) = 1 / value_range;
+                           LatticeAgreement: U, the universe {0..U-1} of set elements, 1 <= U <= 31: an initial
+                           set holds elements v / U and v % U of one v uniform in {0..U*U-1}) */
   int32_t param;        /* OTR/OTR2 afterDecision (Otr.scala:89, default 2); FloodMin f (FloodMin.scala:27);
                            KSet k (KSetAgreement.scala:56); KSetEarlyStopping t; TwoPhaseCommit coord (the
                            io.coord of every process, TwoPhaseCommit.scala:24, 87; 0 <= coord < n, default 0);
@@ -169,11 +173,14 @@ typedef struct psg_instance_summary {
  * values themselves come from the _f64 entry points below. */
 typedef struct psg_process_record {
   int32_t decision;       /* value passed to ConsensusIO.decide (BenOr: 0/1); 0 if none. TwoPhaseCommit: 1 / 0
-                             for TpcIO.decide(Some(true / false)), PSG_NONE32 for decide(None) and for no callback */
+                             for TpcIO.decide(Some(true / false)), PSG_NONE32 for decide(None) and for no callback.
+                             LatticeAgreement: the decided set as a bit mask (bit e = element e, bit 31 never
+                             set), 0 if none; the empty set is also 0: decision_round tells them apart */
   int32_t decision_round; /* round k (0-based) of the first decide callback, -1 if none (TwoPhaseCommit:
                              decide(None), "coordinator suspected", is not a decision: -1) */
   int32_t halt_round;     /* round k whose update called exitAtEndOfRound, -1 if never */
-  int32_t final_x;        /* final main variable (OTR/LV/FloodMin x, BenOr x, KSet pick(t), TwoPhaseCommit vote) */
+  int32_t final_x;        /* final main variable (OTR/LV/FloodMin x, BenOr x, KSet pick(t), TwoPhaseCommit vote,
+                             LatticeAgreement proposed as a bit mask) */
 } psg_process_record;
 
 /* ---------------------------------------------------------------------------
@@ -194,11 +201,11 @@ typedef struct psg_process_record {
 /* Process-state fields visible to a Spec (the variables the reference specs read). */
 enum psg_field {
   PSG_FIELD_X = 0,        /* x (OTR/LV/FloodMin/SLV), est (KSetEarlyStopping), pick(t) (KSet), x (BenOr 0/1),
-                             vote (TwoPhaseCommit 0/1) */
+                             vote (TwoPhaseCommit 0/1), proposed (LatticeAgreement, a set as a bit mask >= 0) */
   PSG_FIELD_DECIDED = 1,  /* decided flag (ghost for algorithms without one: decide callback fired;
                              TwoPhaseCommit: decision.isDefined) */
   PSG_FIELD_DECISION = 2, /* decision (OTR2: Option, PSG_NONE32 when empty; TwoPhaseCommit: Option[Boolean],
-                             PSG_NONE32 / 0 / 1) */
+                             PSG_NONE32 / 0 / 1; LatticeAgreement: Option[Set[Int]], PSG_NONE32 or the bit mask) */
   PSG_FIELD_TS = 3,       /* LastVoting / ShortLastVoting ts */
   PSG_FIELD_READY = 4,    /* LastVoting ready */
   PSG_FIELD_COMMIT = 5,   /* LastVoting / ShortLastVoting commit */

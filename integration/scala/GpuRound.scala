@@ -69,7 +69,10 @@ object GpuRound {
     "example.ShortLastVoting" -> 7, "example.KSetEarlyStopping" -> 8, "example.EpsilonConsensus" -> 9,
     // TpcIO (coord, canCommit, decide(Option[Boolean])) is not a ConsensusIO: inputs are the votes 0 / 1,
     // psg_config.param the coordinator, decisions 1 / 0 / PSG_NONE32 (INTEGRATION.md)
-    "example.TwoPhaseCommit" -> 10)
+    "example.TwoPhaseCommit" -> 10,
+    // LatticeIO (initialValue: Set[Int], decide(Set[Int])) is not a ConsensusIO: inputs and decisions are
+    // subsets of {0..30} as int32 bit masks, psg_config.value_range the universe size (INTEGRATION.md)
+    "example.LatticeAgreement" -> 11)
   private val realValued = Set(9)
 
   def algId(alg: Algorithm[_, _]): Int =

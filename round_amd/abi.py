@@ -17,6 +17,7 @@ PSG_ALG_SLV = 7
 PSG_ALG_KSET_ES = 8
 PSG_ALG_EPSILON = 9
 PSG_ALG_TPC = 10
+PSG_ALG_LATTICE = 11
 
 PSG_TIE_CHAMP = 0
 PSG_TIE_MIN_PID = 1
@@ -47,6 +48,7 @@ CLASS_TO_ALG = {
     "example.KSetEarlyStopping": PSG_ALG_KSET_ES,
     "example.EpsilonConsensus": PSG_ALG_EPSILON,
     "example.TwoPhaseCommit": PSG_ALG_TPC,
+    "example.LatticeAgreement": PSG_ALG_LATTICE,
 }
 
 # Check-slot names per algorithm (psg_check_name). Slot 0 of OTR/LV/BenOr is
@@ -65,6 +67,7 @@ CHECK_NAMES = {
     PSG_ALG_KSET_ES: ["KAgreement", "KValidity"],
     PSG_ALG_EPSILON: ["EpsAgreement", "EpsValidity", "SafetyPredicate"],
     PSG_ALG_TPC: ["Safety", "Invariant0", "UniformAgreement", "Validity"],
+    PSG_ALG_LATTICE: ["Safety", "Invariant0", "Comparability", "DownwardValidity", "UpwardValidity", "Irrevocability"],
 }
 # Slots whose falsity is a violation (invariant slots are informational: an
 # individual invariant of a sequence legitimately fails before/after its phase;
@@ -81,6 +84,7 @@ VIOLATION_SLOTS = {
     PSG_ALG_KSET_ES: [0, 1],
     PSG_ALG_EPSILON: [0, 1],
     PSG_ALG_TPC: [0, 2, 3],
+    PSG_ALG_LATTICE: [0, 2, 3, 4, 5],
 }
 
 

@@ -21,7 +21,7 @@ the device, keep the ones that get closest to a violation.
     predicate in at least `live_rounds` rounds; the target is non-termination
     within R rounds (term_round == never).
   * fault models: general omission (OTR, OTR2, LastVoting, ShortLastVoting,
-    BenOr, EpsilonConsensus, TwoPhaseCommit) or crash-stop with at most f crashes (FloodMin,
+    BenOr, EpsilonConsensus, TwoPhaseCommit, LatticeAgreement) or crash-stop with at most f crashes (FloodMin,
     KSetAgreement, KSetEarlyStopping — their runners' fault model).
 Every counterexample is shrunk (batched delta debugging: all candidate
 simplifications of one step run as one GPU batch) and can be written to a
@@ -110,6 +110,8 @@ def default_model(alg: psync.Algorithm, n: int) -> Model:
         return Model("crash", fmax=alg.param)
     if a == abi.PSG_ALG_TPC:
         return Model("omission")  # (its livenessPredicate: schedules.fixed_coord_live; no liveness search)
+    if a == abi.PSG_ALG_LATTICE:
+        return Model("omission")  # (TrivialSpec: no livenessPredicate to assume, no liveness search)
     raise ValueError(f"no fault model for {alg.class_name}")
 
 
@@ -121,6 +123,9 @@ def default_init(alg: psync.Algorithm, rng, I: int, n: int, values: int) -> np.n
         return rng.integers(0, 2, (I, n), dtype=np.int32)
     if alg.alg_id == abi.PSG_ALG_TPC:  # votes io.canCommit, mostly yes: no w.p. 1 / values
         return (rng.integers(0, max(values, 1), (I, n)) != 0).astype(np.int32)
+    if alg.alg_id == abi.PSG_ALG_LATTICE:  # subsets of {0..values-1} as bit masks: lattice_init's one or two elements
+        v = rng.integers(0, values * values, (I, n))
+        return ((1 << (v // values)) | (1 << (v % values))).astype(np.int32)
     return rng.integers(1, values + 1, (I, n), dtype=np.int32)  # nonzero (LastVoting.scala:134)
 
 

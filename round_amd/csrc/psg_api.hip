@@ -32,6 +32,7 @@ __global__ void gen_init_kernel(uint64_t inst_begin, uint64_t count, int n, int 
     const uint64_t w = rword(seed, inst_begin + i, ROUND_INIT, (uint32_t)p, 0);
     out[e] = alg == PSG_ALG_BENOR ? (int32_t)((uint32_t)w & 1u)
              : alg == PSG_ALG_TPC ? tpc_vote((uint32_t)w, (uint32_t)V)
+             : alg == PSG_ALG_LATTICE ? lattice_init((uint32_t)w, (uint32_t)V)
                                   : 1 + (int32_t)mulhi32((uint32_t)w, (uint32_t)V);
   }
 }
@@ -144,6 +145,8 @@ static const char* const k_names_benor[] = {"Safety", "Invariant0", "Agreement",
 static const char* const k_names_k[] = {"KAgreement", "KValidity"};
 static const char* const k_names_eps[] = {"EpsAgreement", "EpsValidity", "SafetyPredicate"};
 static const char* const k_names_tpc[] = {"Safety", "Invariant0", "UniformAgreement", "Validity"};
+static const char* const k_names_lattice[] = {"Safety", "Invariant0", "Comparability", "DownwardValidity", "UpwardValidity",
+                                              "Irrevocability"};
 // the kernels record and flush exactly the named slots (psg_device.hpp)
 static_assert(std::size(k_names_otr) == kOtrChecks, "k_names_otr and kOtrChecks disagree");
 static_assert(std::size(k_names_lv) == kLvChecks, "k_names_lv and kLvChecks disagree");
@@ -151,6 +154,7 @@ static_assert(std::size(k_names_benor) == kBenOrChecks, "k_names_benor and kBenO
 static_assert(std::size(k_names_k) == kKAgreeChecks, "k_names_k and kKAgreeChecks disagree");
 static_assert(std::size(k_names_eps) == kEpsilonChecks, "k_names_eps and kEpsilonChecks disagree");
 static_assert(std::size(k_names_tpc) == kTpcChecks, "k_names_tpc and kTpcChecks disagree");
+static_assert(std::size(k_names_lattice) == kLatticeChecks, "k_names_lattice and kLatticeChecks disagree");
 
 struct CheckNames {
   const char* const* name;
@@ -263,10 +267,21 @@ static const AlgRow k_algs[] = {
        return c.param < 0 || c.param >= c.n ? "TwoPhaseCommit needs 0 <= coord < n" : nullptr;
      },
      launch_tpc, tpc_kernel_ptr},
+    {"example.LatticeAgreement", k_names_lattice,
+     [](psg_config& c, int) {  // sets over {0..15}; a quarter of the links lost, no good rounds
+       c.rounds = 8;
+       c.value_range = 16;
+       c.sched.drop_log2 = 2;
+       c.sched.good_p32 = 0;
+     },
+     [](const psg_config& c) -> const char* {  // a set is an int32 bit mask >= 0: elements 0..30
+       return c.value_range < 1 || c.value_range > 31 ? "LatticeAgreement needs 1 <= value_range <= 31" : nullptr;
+     },
+     launch_lattice, lattice_kernel_ptr},
 };
 
 constexpr int k_alg_rows = (int)(sizeof(k_algs) / sizeof(k_algs[0]));
-static_assert(k_alg_rows == PSG_ALG_TPC + 1, "one row per PSG_ALG_*, in the enum's order");
+static_assert(k_alg_rows == PSG_ALG_LATTICE + 1, "one row per PSG_ALG_*, in the enum's order");
 
 // The row of an algorithm id; null: unknown algorithm.
 static const AlgRow* alg_row(int alg) { return alg > 0 && alg < k_alg_rows ? &k_algs[alg] : nullptr; }
@@ -1321,6 +1336,8 @@ static int pop_check(psg_ctx* c, const psg_population_params* p) {
   if (!p) return fail(c, PSG_EINVAL, "null population parameters");
   if (c->cfg.alg == PSG_ALG_EPSILON) return fail(c, PSG_EINVAL, "populations hold int32 inputs (not EpsilonConsensus)");
   if (c->cfg.alg != PSG_ALG_BENOR && p->value_range < 1) return fail(c, PSG_EINVAL, "value_range must be >= 1");
+  if (c->cfg.alg == PSG_ALG_LATTICE && p->value_range > 31)
+    return fail(c, PSG_EINVAL, "LatticeAgreement needs 1 <= value_range <= 31");
   if (p->min_size > c->cfg.n) return fail(c, PSG_EINVAL, "min_size > n");
   return PSG_OK;
 }
@@ -1340,7 +1357,10 @@ static PopArgs pop_args(const psg_ctx* c, const psg_population_params* p, uint64
   for (int j = 0; j < 4; ++j) a.keep[j] = p->keep_p256[j];
   a.V = p->value_range;
   a.redraw = p->redraw_p256;
-  a.init_kind = c->cfg.alg == PSG_ALG_BENOR ? POP_INIT_COIN : c->cfg.alg == PSG_ALG_TPC ? POP_INIT_VOTE : POP_INIT_VALUE;
+  a.init_kind = c->cfg.alg == PSG_ALG_BENOR     ? POP_INIT_COIN
+                : c->cfg.alg == PSG_ALG_TPC     ? POP_INIT_VOTE
+                : c->cfg.alg == PSG_ALG_LATTICE ? POP_INIT_SET
+                                                : POP_INIT_VALUE;
   return a;
 }
 

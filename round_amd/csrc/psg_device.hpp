@@ -123,8 +123,9 @@ struct PopArgs {
   uint32_t redraw;
   int init_kind;  // POP_INIT_*
 };
-// a population's initial values: {1..V}; BenOr's {0, 1} coin bit; TwoPhaseCommit's vote (tpc_vote)
-enum { POP_INIT_VALUE = 0, POP_INIT_COIN = 1, POP_INIT_VOTE = 2 };
+// a population's initial values: {1..V}; BenOr's {0, 1} coin bit; TwoPhaseCommit's vote (tpc_vote);
+// LatticeAgreement's set (lattice_init)
+enum { POP_INIT_VALUE = 0, POP_INIT_COIN = 1, POP_INIT_VOTE = 2, POP_INIT_SET = 3 };
 
 #ifndef PSG_PHASE_TIMERS
 #define PSG_PHASE_TIMERS 0
@@ -289,6 +290,14 @@ PSG_DEV uint32_t mulhi32(uint32_t a, uint32_t b) { return __umulhi(a, b); }
 // TwoPhaseCommit's seeded io.canCommit from the process's init word: the value every other
 // algorithm draws, 1 + mulhi32(w, V) in {1..V}, votes no iff it is 1, so P(no vote) = 1 / V
 PSG_DEV int32_t tpc_vote(uint32_t w, uint32_t V) { return mulhi32(w, V) != 0u ? 1 : 0; }
+
+// LatticeAgreement's seeded io.initialValue from the process's init word: a subset of {0..U-1}
+// as a bit mask, v = mulhi32(w, U * U) uniform in {0..U*U-1}, elements v / U and v % U (one
+// element when they coincide); 1 <= U <= 31 (psg_create), so bit 31 is never set
+PSG_DEV int32_t lattice_init(uint32_t w, uint32_t U) {
+  const uint32_t v = mulhi32(w, U * U);
+  return (int32_t)((1u << (v / U)) | (1u << (v % U)));
+}
 
 // java.util.Random(s).nextBoolean(): BenOr coin (example/BenOr.scala:77)
 PSG_DEV bool java_first_boolean(uint64_t s) {
@@ -984,6 +993,7 @@ struct Sched {
     const uint64_t w = rword(seed, inst, ROUND_INIT, (uint32_t)pid, 0);
     if (alg == PSG_ALG_BENOR) return (int32_t)((uint32_t)w & 1u);
     if (alg == PSG_ALG_TPC) return tpc_vote((uint32_t)w, (uint32_t)V);
+    if (alg == PSG_ALG_LATTICE) return lattice_init((uint32_t)w, (uint32_t)V);
     return 1 + (int32_t)mulhi32((uint32_t)w, (uint32_t)V);
   }
 
@@ -1149,6 +1159,35 @@ struct Sched {
     return assemble(pid, good, goodS, CB, CN, dm, hf);
   }
 };
+
+// HO(pid) of round k: Sched::ho's set, word for word, from the same draw. Only the assembly is
+// written out here, because Sched::assemble adds the self bit through mset, whose word-indexed
+// store compiles at W > 2 to a private array (8 W bytes of scratch in every seeded W = 3, 4
+// round kernel); here the self bit is ORed into every word under a per-word select
+// (TwoPhaseCommit, LatticeAgreement).
+template <int W, bool XHO>
+PSG_DEV Mask<W> ho_select(const Sched<W, XHO>& sc, int k, int pid, bool good, const Mask<W>& goodS, const Mask<W>& CB,
+                       const Mask<W>& CN) {
+  if constexpr (XHO) {
+    return sc.ho(k, pid, good, goodS, CB, CN);
+  } else {
+    uint64_t dm[W], hf[W];
+    uint32_t cw = 0;
+#pragma unroll
+    for (int w = 0; w < W; ++w) cw |= CN.w[w] ? 1u << w : 0u;
+    sc.draw((uint32_t)k, (uint32_t)pid, good, sc.crash_on && cw != 0u, dm, hf, cw);
+    const uint64_t self = sc.self_bit ? 1ull << (pid & 63) : 0ull;
+    Mask<W> base;
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+      base.w[w] = good ? goodS.w[w] : (sc.drop > 0 ? sc.full.w[w] & ~dm[w] : sc.full.w[w]);
+      if (sc.crash_on) base.w[w] &= ~(CB.w[w] | (CN.w[w] & ~hf[w]));
+      base.w[w] |= (pid >> 6) == w ? self : 0ull;
+    }
+    if (sc.ho_min >= 0 && mpopc(base) <= sc.ho_min) base = sc.full;
+    return base;
+  }
+}
 
 // Crash sets of round k: CB = processes crashed before round k, CN = crashing in
 // round k. A process's crash round is fixed per instance, so for W > 1 the
@@ -1480,6 +1519,7 @@ constexpr int kBenOrChecks = 5;    // BenOr
 constexpr int kKAgreeChecks = 2;   // FloodMin, KSet, ShortLastVoting, KSetEarlyStopping
 constexpr int kEpsilonChecks = 3;  // EpsilonConsensus
 constexpr int kTpcChecks = 4;      // TwoPhaseCommit
+constexpr int kLatticeChecks = 6;  // LatticeAgreement
 // The check slots and the Checks a kernel with hook SH reports: the fused Spec's, else the built-in ones.
 template <class SH>
 PSG_DEV constexpr int hook_slots(int builtin) { return SH::kFused ? SH::kSlots : builtin; }

@@ -33,6 +33,7 @@ hipError_t launch_slv(const KArgs& a, int W, int grid, hipStream_t s);
 hipError_t launch_kset_es(const KArgs& a, int W, int grid, hipStream_t s);
 hipError_t launch_epsilon(const KArgs& a, int W, int grid, hipStream_t s);
 hipError_t launch_tpc(const KArgs& a, int W, int grid, hipStream_t s);
+hipError_t launch_lattice(const KArgs& a, int W, int grid, hipStream_t s);
 
 const void* otr_kernel_ptr(int W);
 const void* lv_kernel_ptr(int W);
@@ -44,6 +45,7 @@ const void* slv_kernel_ptr(int W);
 const void* kset_es_kernel_ptr(int W);
 const void* epsilon_kernel_ptr(int W);
 const void* tpc_kernel_ptr(int W);
+const void* lattice_kernel_ptr(int W);
 
 hipError_t launch_champ_selftest(const uint64_t* sets, int count, int tiebreak, int32_t* out, hipStream_t s);
 hipError_t launch_schedule(const KArgs& a, int W, int grid, uint64_t* ho_out, int32_t* crash_out, hipStream_t s);

@@ -122,6 +122,7 @@ __global__ void __launch_bounds__(256) pop_init_kernel(PopArgs a) {
     const U4 o = pop_draw(a, i, p, TAG_INIT);
     const int32_t fresh = a.init_kind == POP_INIT_COIN   ? (int32_t)(o.y & 1u)
                           : a.init_kind == POP_INIT_VOTE ? tpc_vote(o.y, (uint32_t)a.V)
+                          : a.init_kind == POP_INIT_SET  ? lattice_init(o.y, (uint32_t)a.V)
                                                          : 1 + (int32_t)mulhi32(o.y, (uint32_t)a.V);
     int32_t v = fresh;
     if (op != 2) {

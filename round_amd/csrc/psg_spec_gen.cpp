@@ -1216,6 +1216,7 @@ bool fused_kernel(int alg, std::string& src, std::string& body, std::string& tar
     case PSG_ALG_SLV: src = "psg_slv.hip"; body = "slv_body"; break;
     case PSG_ALG_KSET_ES: src = "psg_kset_es.hip"; body = "kset_es_body"; break;
     case PSG_ALG_TPC: src = "psg_tpc.hip"; body = "tpc_body"; break;
+    case PSG_ALG_LATTICE: src = "psg_lattice.hip"; body = "lattice_body"; break;
     default: return false;
   }
   targs_w_prefix.clear();

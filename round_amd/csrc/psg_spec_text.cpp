@@ -321,6 +321,8 @@ std::set<int> alg_fields(int alg) {
     case PSG_ALG_SLV:
       return S{PSG_FIELD_X, PSG_FIELD_DECIDED, PSG_FIELD_DECISION, PSG_FIELD_TS, PSG_FIELD_COMMIT, PSG_FIELD_VOTE,
                PSG_FIELD_HOSIZE};
+    case PSG_ALG_LATTICE:
+      return S{PSG_FIELD_X, PSG_FIELD_DECIDED, PSG_FIELD_DECISION, PSG_FIELD_HOSIZE};
     case PSG_ALG_TPC:
       return S{PSG_FIELD_X, PSG_FIELD_DECIDED, PSG_FIELD_DECISION, PSG_FIELD_VOTE, PSG_FIELD_HOSIZE};
   }

@@ -26,34 +26,6 @@
 
 namespace psg {
 
-// HO(pid) of round k: Sched::ho's set, word for word, from the same draw. Only the assembly is
-// written out here, because Sched::assemble adds the self bit through mset, whose word-indexed
-// store compiles at W > 2 to a private array (8 W bytes of scratch in every seeded W = 3, 4
-// round kernel); here the self bit is ORed into every word under a per-word select.
-template <int W, bool XHO>
-PSG_DEV Mask<W> tpc_ho(const Sched<W, XHO>& sc, int k, int pid, bool good, const Mask<W>& goodS, const Mask<W>& CB,
-                       const Mask<W>& CN) {
-  if constexpr (XHO) {
-    return sc.ho(k, pid, good, goodS, CB, CN);
-  } else {
-    uint64_t dm[W], hf[W];
-    uint32_t cw = 0;
-#pragma unroll
-    for (int w = 0; w < W; ++w) cw |= CN.w[w] ? 1u << w : 0u;
-    sc.draw((uint32_t)k, (uint32_t)pid, good, sc.crash_on && cw != 0u, dm, hf, cw);
-    const uint64_t self = sc.self_bit ? 1ull << (pid & 63) : 0ull;
-    Mask<W> base;
-#pragma unroll
-    for (int w = 0; w < W; ++w) {
-      base.w[w] = good ? goodS.w[w] : (sc.drop > 0 ? sc.full.w[w] & ~dm[w] : sc.full.w[w]);
-      if (sc.crash_on) base.w[w] &= ~(CB.w[w] | (CN.w[w] & ~hf[w]));
-      base.w[w] |= (pid >> 6) == w ? self : 0ull;
-    }
-    if (sc.ho_min >= 0 && mpopc(base) <= sc.ho_min) base = sc.full;
-    return base;
-  }
-}
-
 // Kernel body; SH: the Spec hook (NoHook in psg_device.hpp).
 template <int W, bool XHO, class SH = NoHook, bool TR = true>
 PSG_DEV void tpc_body(const KArgs& a) {
@@ -109,7 +81,7 @@ PSG_DEV void tpc_body(const KArgs& a) {
       const bool good = sc.good_round(k, g.lane, a.R, goodS);
       Mask<W> CB = mzero<W>(), CN = mzero<W>();
       if (sc.crash_on) in.cs.sets(g, k, CB, CN);
-      return tpc_ho<W, XHO>(sc, k, pid, good, goodS, CB, CN);
+      return ho_select<W, XHO>(sc, k, pid, good, goodS, CB, CN);
     };
     // round k = RS of the first phase (compile time: each slot's step specialized); nobody has
     // halted before round 2, so every process sends and the coordinator is alive

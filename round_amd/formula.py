@@ -54,6 +54,7 @@ ALG_FIELDS = {
     abi.PSG_ALG_SLV: {FIELD_X, FIELD_DECIDED, FIELD_DECISION, FIELD_TS, FIELD_COMMIT, FIELD_VOTE, FIELD_HOSIZE},
     abi.PSG_ALG_KSET_ES: {FIELD_X, FIELD_DECIDED, FIELD_DECISION, FIELD_HOSIZE},
     abi.PSG_ALG_TPC: {FIELD_X, FIELD_DECIDED, FIELD_DECISION, FIELD_VOTE, FIELD_HOSIZE},
+    abi.PSG_ALG_LATTICE: {FIELD_X, FIELD_DECIDED, FIELD_DECISION, FIELD_HOSIZE},
 }
 
 
@@ -716,7 +717,7 @@ REFERENCE_SPECS = {
 # algorithms whose round kernel a fused module instantiates with the Spec as its check hook
 FUSED_KERNELS = frozenset({abi.PSG_ALG_OTR, abi.PSG_ALG_OTR2, abi.PSG_ALG_LAST_VOTING, abi.PSG_ALG_FLOODMIN,
                            abi.PSG_ALG_KSET, abi.PSG_ALG_BENOR, abi.PSG_ALG_SLV, abi.PSG_ALG_KSET_ES,
-                           abi.PSG_ALG_TPC})
+                           abi.PSG_ALG_TPC, abi.PSG_ALG_LATTICE})
 
 # Generator options, on only for A/B measurements (PSG_SPEC_OPTIONS, include/psg.h): the
 # symmetric-check-point lowering (spec::uniform) and the split foralls / hoisted conjuncts.

@@ -241,9 +241,31 @@ class TwoPhaseCommit(Algorithm):
         return 2 * n  # seeded votes: no w.p. 1 / value_range, so both outcomes stay common at any n
 
 
+class LatticeAgreement(Algorithm):
+    """example.LatticeAgreement(rt, timeout) — example/LatticeAgreement.scala:70 (one round per phase,
+    lattice agreement over Set[Int]). A set is a subset of {0..30} held as an int32 bit mask (bit e =
+    element e), bottom is 0 and join is OR; inputs are the sets io.initialValue, `value_range` is the
+    universe size U (1..31) of the seeded ones. A decision is the decided set's mask; the empty set
+    and "none" are both 0 and differ in decision_round."""
+    class_name = "example.LatticeAgreement"
+    alg_id = abi.PSG_ALG_LATTICE
+
+    def __init__(self, variant=0):
+        super().__init__(0, variant)
+
+    def default_schedule(self, n):
+        return HOSchedule(drop_log2=2, good_round=0.0)
+
+    def default_rounds(self, n):
+        return 8
+
+    def default_value_range(self, n):
+        return 16
+
+
 ALGORITHMS = {c.class_name: c for c in (OTR, LastVoting, FloodMin, KSetAgreement, BenOr,
                                           OTR2, ShortLastVoting, KSetEarlyStopping, EpsilonConsensus,
-                                          TwoPhaseCommit)}
+                                          TwoPhaseCommit, LatticeAgreement)}
 
 
 def make_config(alg: Algorithm, n: int, rounds: Optional[int] = None, seed: int = 1,

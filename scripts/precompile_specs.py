@@ -37,6 +37,10 @@ def jobs():
     out.append(("ref", abi.PSG_ALG_TPC, False, None))
     out.append(("ref", abi.PSG_ALG_TPC, True, 8))
     out.append(("ref", abi.PSG_ALG_TPC, True, 130))
+    # tests/test_gpu_lattice.py: LatticeAgreement's custom Spec native, and fused at W = 1 and W = 3
+    out.append(("lattice_custom", abi.PSG_ALG_LATTICE, False, None))
+    out.append(("lattice_custom", abi.PSG_ALG_LATTICE, True, 8))
+    out.append(("lattice_custom", abi.PSG_ALG_LATTICE, True, 130))
     # tests/test_gpu_rounds.py: the reference Spec plus a property over |HO(p)|, fused
     out.append(("ref_ho", abi.PSG_ALG_OTR, True, 64))
     out.append(("ref_ho", abi.PSG_ALG_LAST_VOTING, True, 64))
@@ -68,6 +72,9 @@ def build(job):
         spec = spec_cases.ref_with_ho_bound(alg)
     elif kind == "lv_custom":
         spec = spec_cases.lv_custom()
+    elif kind == "lattice_custom":
+        import test_gpu_lattice
+        spec = test_gpu_lattice.custom_spec()
     else:
         spec = dict((c[0], c[4]) for c in spec_cases.CUSTOM)[kind]()
     p = F.compile_native(spec, alg, fused=fused, n=n)

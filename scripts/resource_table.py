@@ -8,7 +8,7 @@ import sys
 
 SRC = "round_amd/csrc"
 FILES = ["psg_otr.hip", "psg_lv.hip", "psg_floodmin.hip", "psg_kset.hip", "psg_benor.hip", "psg_slv.hip",
-         "psg_kset_es.hip", "psg_epsilon.hip", "psg_tpc.hip", "psg_schedule.hip"]
+         "psg_kset_es.hip", "psg_epsilon.hip", "psg_tpc.hip", "psg_lattice.hip", "psg_schedule.hip"]
 FIELDS = {"TotalSGPRs": "sgpr", "VGPRs": "vgpr", "ScratchSize [bytes/lane]": "scratch",
           "Occupancy [waves/SIMD]": "waves", "SGPRs Spill": "sgpr_spill", "VGPRs Spill": "vgpr_spill"}
 
