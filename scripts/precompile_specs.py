@@ -18,9 +18,8 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 def jobs():
     from round_amd import abi, formula as F
     import spec_cases
-    import test_gpu_spec as T
     out = []
-    for _, alg, n, _, _ in T.REF:
+    for _, alg, n, _, _ in spec_cases.REF:
         out.append(("ref", alg.alg_id, False, None))
         out.append(("ref", alg.alg_id, True, n))
     for cid, alg, n, _, _ in spec_cases.CUSTOM:
@@ -50,9 +49,8 @@ def jobs():
                  (abi.PSG_ALG_BENOR, 128)):
         out.append(("text", a, True, n))
     # tests/test_gpu_instantiations.py: every fused algorithm at W = 1..4
-    import test_gpu_instantiations as TI
-    for name, n in TI.fused_modules():
-        out.append(("inst:" + name, TI.ALG_ID[name], True, n))
+    for name, n in spec_cases.fused_modules():
+        out.append(("inst:" + name, spec_cases.ALG_ID[name], True, n))
     return sorted(set(out), key=str)
 
 
@@ -66,15 +64,13 @@ def build(job):
     if kind in ("ref", "fusedbuild"):
         spec = F.REFERENCE_SPECS[alg]() if alg in F.REFERENCE_SPECS else spec_cases.uniform_agreement()
     elif kind.startswith("inst:"):
-        import test_gpu_instantiations as TI
-        spec = TI.spec_of(kind[5:])
+        spec = spec_cases.spec_of(kind[5:])
     elif kind == "ref_ho":
         spec = spec_cases.ref_with_ho_bound(alg)
     elif kind == "lv_custom":
         spec = spec_cases.lv_custom()
     elif kind == "lattice_custom":
-        import test_gpu_lattice
-        spec = test_gpu_lattice.custom_spec()
+        spec = spec_cases.lattice_custom()
     else:
         spec = dict((c[0], c[4]) for c in spec_cases.CUSTOM)[kind]()
     p = F.compile_native(spec, alg, fused=fused, n=n)

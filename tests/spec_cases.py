@@ -1,5 +1,7 @@
-"""Custom Spec programs shared by the CPU (test_formula.py) and GPU (test_gpu_spec.py) tests."""
-from round_amd import formula as F, psync
+"""Spec programs and their case tables, shared by the CPU tests (test_formula.py, test_spec_text.py), the
+GPU tests (test_gpu_spec.py, test_gpu_instantiations.py, ...) and scripts/precompile_specs.py, which
+compiles every module the GPU tests load."""
+from round_amd import abi, formula as F, psync
 
 P, V, VB, n, r, init, old = F.P, F.V, F.VB, F.n, F.r, F.init, F.old
 H = psync.HOSchedule
@@ -195,6 +197,21 @@ def ref_with_ho_bound(alg_id):
     return spec
 
 
+def lattice_custom():
+    """LatticeAgreement (tests/test_gpu_lattice.py), on the existing operators (the Formula language
+    has no set operators): a defined decision equals proposed; proposed never falls below its
+    initial value (a superset's mask is never numerically smaller); Irrevocability; every live
+    process hears more than 2n/3 (fails often)."""
+    return F.Spec(properties=[
+        ("Termination", P.forall(lambda i: i.decided)),
+        ("DecisionIsProposed", P.forall(lambda i: i.decided.implies(i.decision == i.x))),
+        ("Grows", P.forall(lambda i: i.x >= init(i.x))),
+        ("Irrevocability", P.forall(lambda i: old(i.decided).implies(i.decided & (old(i.decision) == i.decision)))),
+        ("HearsTwoThirds", P.forall(lambda i: i.HO.size > 2 * n // 3)),
+        ("OneSet", P.forall(lambda i: P.forall(lambda j: i.x == j.x))),
+    ])
+
+
 # (id, algorithm, n, make_config kwargs, spec factory)
 CUSTOM = [
     ("fm-n12", psync.FloodMin(2), 12, dict(value_range=8, schedule=H(drop_log2=0, good_round=0.0, crash_fmax=3)),
@@ -252,3 +269,78 @@ CUSTOM = [
     ("fm-n12-termcse", psync.FloodMin(2), 12, dict(value_range=4, schedule=H(drop_log2=0, good_round=0.0,
                                                                               crash_fmax=3)), term_shared_shapes),
 ]
+
+# The reference Specs against the built-in checks (tests/test_gpu_spec.py):
+# (id, algorithm, n, instances, make_config kwargs)
+REF = [
+    ("otr-n64", psync.OTR(), 64, 600, dict(value_range=8, seed=3)),
+    ("otr-mutant-n8", psync.OTR(variant=1), 8, 2000, dict(schedule=H(drop_log2=1, good_round=0.0), seed=4)),
+    ("otr-n100-W2", psync.OTR(), 100, 100, dict(value_range=4, seed=5)),
+    ("otr2-n64", psync.OTR2(), 64, 500, dict(value_range=4, seed=6)),
+    ("lv-n16-loss", psync.LastVoting(), 16, 500, dict(value_range=3, seed=7, schedule=H(
+        drop_log2=1, good_round=0.0, crash_fmax=7))),
+    ("lv-mutant-n6", psync.LastVoting(variant=1), 6, 1500, dict(value_range=5, seed=8)),
+    ("lv-n64", psync.LastVoting(), 64, 200, dict(seed=9, rounds=12)),
+    ("benor-n8", psync.BenOr(), 8, 1500, dict(seed=10)),
+    ("benor-n128-W2", psync.BenOr(), 128, 40, dict(seed=11, rounds=16)),
+]
+
+# tests/test_gpu_instantiations.py: the algorithms by short name, the Spec each runs under
+# psg_run_batch_spec, and the (algorithm, n) of its fused modules
+ALG_ID = dict(otr=abi.PSG_ALG_OTR, otr2=abi.PSG_ALG_OTR2, lv=abi.PSG_ALG_LAST_VOTING, slv=abi.PSG_ALG_SLV,
+              fm=abi.PSG_ALG_FLOODMIN, kset=abi.PSG_ALG_KSET, kses=abi.PSG_ALG_KSET_ES, benor=abi.PSG_ALG_BENOR,
+              eps=abi.PSG_ALG_EPSILON, tpc=abi.PSG_ALG_TPC)
+SPEC_ALGS = ("otr", "otr2", "lv", "slv", "fm", "kset", "kses", "benor", "tpc")  # every algorithm but eps (Double state)
+FUSED_N = (65, 129, 193)         # seeded: the ragged n of every W > 1
+FUSED_X_N = (64, 65, 129, 193)   # under a loaded schedule
+
+
+def spec_of(alg):
+    aid = ALG_ID[alg]
+    if aid in F.REFERENCE_SPECS:
+        return F.REFERENCE_SPECS[aid]()
+    return at_most_two_decisions() if alg in ("kset", "kses") else uniform_agreement()
+
+
+def fused_modules():
+    """(algorithm, n) of every fused module tests/test_gpu_instantiations.py loads."""
+    return sorted({(a, n) for a in SPEC_ALGS for n in FUSED_N + FUSED_X_N})
+
+
+# Hand-written Formula texts in the shapes FormulaExtractor produces (tests/test_spec_text.py has the
+# DSL equivalent of each): a `val A = ...` let, flattened multi-variable binders, n-ary And.
+LV_MAJORITY_LET = """
+(Spec (phase 1)
+  (invariants
+    (Exists ((v Int) (t Int))
+      (Exists ((A Set))
+        (App And (App Eq (Var A) (Comprehension ((i pid)) (App Geq (App ts (Var i)) (Var t))))
+                 (App Gt (App Cardinality (Var A)) (App Divides (Var n) (Lit 2)))
+                 (App Gt (Var r) (Lit 0))
+                 (App Leq (Var t) (App Divides (Var r) (Lit 4)))
+                 (ForAll ((i pid)) (App Implies (App In (Var i) (Var A)) (App Eq (App x (Var i)) (Var v)))))))))
+"""
+
+AGREEMENT_FLAT = """
+(Spec (phase 1) (invariants)
+  (properties
+    (prop "Agreement" (ForAll ((i pid) (j pid))
+        (App Implies (App And (App decided (Var i)) (App decided (Var j)))
+                     (App Eq (App decision (Var i)) (App decision (Var j))))))
+    (prop "Irrevocability" (ForAll ((i pid))
+        (App Implies (App __old__decided (Var i))
+                     (App And (App decided (Var i)) (App Eq (App __old__decision (Var i)) (App decision (Var i)))))))
+    (prop "Termination" (ForAll ((i pid)) (App decided (Var i))))))
+"""
+
+NARY_AND = """
+(Spec (phase 1)
+  (invariants (ForAll ((i pid)) (App And (App Not (App decided (Var i))) (App Geq (App x (Var i)) (Lit 1))
+                                         (App Leq (App x (Var i)) (Lit 100000)) (Lit true))))
+  (safetyPredicate (ForAll ((p pid)) (App Gt (App Cardinality (App HO (Var p))) (App Divides (Var n) (Lit 2))))))
+"""
+
+
+def same_program(a, b):
+    assert (a.code, a.slot_entry, a.slot_flags, a.term_entry, a.n_vars, a.slot_names) == \
+           (b.code, b.slot_entry, b.slot_flags, b.term_entry, b.n_vars, b.slot_names)

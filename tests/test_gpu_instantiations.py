@@ -75,21 +75,17 @@ import pytest
 from round_amd import abi, formula as F, lib, psync, schedules as S
 
 import spec_cases
-from test_gpu_parity import F64_ABS_TOL, _check_eps, _cmp_summary, _inst_tuple, _rec_tuple  # noqa: F401
-from test_gpu_rounds import BEGIN, assert_run_equals_oracle, run_any, schedule_cfg, tpc_seeded
-from test_gpu_schedule import _init, _schedule
-from test_gpu_tpc import _seeded_votes, assert_equal_to_restatement, digest_of, gpu_explicit  # noqa: F401
-from test_reference_tpc import ho_ints, py_tpc
+from gpu_support import (BEGIN, F64_ABS_TOL, assert_equal_to_restatement, assert_run_equals_oracle, cmp_instances,
+                         cmp_summary, gpu_explicit, inst_tuple, np_inst_tuple, random_init, random_schedule, rec_tuple,
+                         run_any, schedule_cfg, seeded_votes, spec_rows, tpc_seeded)
+from restatement import M64, digest_of, ho_ints, py_tpc
+from spec_cases import ALG_ID, FUSED_N, FUSED_X_N, spec_of
 
 gpu = pytest.mark.gpu
 H = psync.HOSchedule
-M64 = (1 << 64) - 1
 I32MIN, I32MAX = -(1 << 31), (1 << 31) - 1
 
 ALGS = ("otr", "otr2", "lv", "slv", "fm", "kset", "kses", "benor", "eps", "tpc")
-ALG_ID = dict(otr=abi.PSG_ALG_OTR, otr2=abi.PSG_ALG_OTR2, lv=abi.PSG_ALG_LAST_VOTING, slv=abi.PSG_ALG_SLV,
-              fm=abi.PSG_ALG_FLOODMIN, kset=abi.PSG_ALG_KSET, kses=abi.PSG_ALG_KSET_ES, benor=abi.PSG_ALG_BENOR,
-              eps=abi.PSG_ALG_EPSILON, tpc=abi.PSG_ALG_TPC)
 WIDE = (65, 128, 129, 192, 193, 256)  # per W > 1: last word holds one process / is full
 NARROW = (63, 64)
 
@@ -188,7 +184,8 @@ ROWS = [
                                                                                           good_round=0.0))),
 ]
 ROW = {r.name: r for r in ROWS}
-TRACED_ROWS = ("otr", "otr2", "lv", "slv", "fm", "kset", "kses", "benor", "tpc")
+TRACED_ROWS = spec_cases.SPEC_ALGS
+assert all(ROW[r].alg == r for r in TRACED_ROWS)  # spec_cases.fused_modules() names the modules by these
 
 # Seeds: 3, except where the crash guard needs another one. With at most 1..4 crashes among n
 # processes, process n - 1 of a ragged n crashes in few instances; these seeds are the first of
@@ -210,13 +207,6 @@ def case_cfg(row, n):
     return psync.make_config(r.make(n), n, seed=seed_of(row, n), batch_capacity=count_of(row, n), **r.kw(n))
 
 
-def spec_of(alg):
-    aid = ALG_ID[alg]
-    if aid in F.REFERENCE_SPECS:
-        return F.REFERENCE_SPECS[aid]()
-    return spec_cases.at_most_two_decisions() if alg in ("kset", "kses") else spec_cases.uniform_agreement()
-
-
 Oracle = collections.namedtuple("Oracle", "cfg osum opi orec dec dround crash runs")
 _ORACLE = {}
 
@@ -235,7 +225,7 @@ def oracle_case(oracle_mod, row, n):
                              np.int32)
         if r.alg == "tpc":
             ho, _ = oracle_mod.materialize_schedule(schedule_cfg(cfg), BEGIN, cnt)
-            votes = _seeded_votes(cfg, oracle_mod, BEGIN, cnt)
+            votes = seeded_votes(cfg, oracle_mod, BEGIN, cnt)
             runs = [py_tpc(n, cfg.param, votes[i], ho_ints(ho[i]), cfg.rounds) for i in range(cnt)]
             orec = None
             dec = np.array([[x[0] for x in run.rec] for run in runs], np.float64)
@@ -275,8 +265,7 @@ def sample_of(cnt):
 
 SEEDED = [(r.name, n) for r in ROWS for n in WIDE]
 TRACED = [(row, n) for row in TRACED_ROWS for n in NARROW + WIDE]
-FUSED = [(row, n) for row in TRACED_ROWS for n in (65, 129, 193)]
-FUSED_X_N = (64, 65, 129, 193)
+FUSED = [(row, n) for row in TRACED_ROWS for n in FUSED_N]
 
 
 def _ids(cases):
@@ -301,10 +290,6 @@ def test_seeded_matches_oracle(row, n, oracle_mod):
             run_any(gr, oracle_mod, cnt, sample_of(cnt))
         else:
             assert_run_equals_oracle(gr, cnt, o.osum, o.opi, o.orec, sample_of(cnt))
-
-
-def _spec_rows(pi, k):
-    return [(tuple(s.first_fail)[:k], s.term_round) for s in pi]
 
 
 def traced_program(alg, n):
@@ -349,7 +334,7 @@ def assert_traced_equals_oracle(alg, o, n, cnt, prog, sp, dec, dround, oracle_mo
     bad = np.nonzero((np.array(dec, np.float64).reshape(cnt, n) != o.dec)
                      | (np.array(dround, np.int64).reshape(cnt, n) != o.dround))
     assert bad[0].size == 0, f"decisions differ, first (instance, process) {(int(bad[0][0]), int(bad[1][0]))}"
-    got_spec = _spec_rows(sp.per_instance, k)
+    got_spec = spec_rows(sp.per_instance, k)
     for s in range(k):  # counters agree with the per-instance view
         assert sp.summary.fail_count[s] == sum(1 for f, _ in got_spec if f[s] != abi.PSG_NEVER)
     if want_spec is not None:
@@ -392,7 +377,7 @@ def test_traced_epsilon_is_refused():
 
 
 # ------------------------------------------------------------------------------------ explicit schedules
-# name -> (algorithm, R, schedule family of test_gpu_schedule._schedule)
+# name -> (algorithm, R, schedule family of gpu_support.random_schedule)
 EXPLICIT = {
     "otr": (lambda n: psync.OTR(), 8, "omission"),
     "otr2": (lambda n: psync.OTR2(), 8, "omission"),
@@ -413,7 +398,7 @@ EXPLICIT_CASES = [(a, n) for a in ALGS for n in ((NARROW if a in ("otr2", "kset"
 
 
 def silence_some_crashed(ho, crash, n):
-    """A crash-stop schedule of test_gpu_schedule._schedule, changed in every second instance that
+    """A crash-stop schedule of gpu_support.random_schedule, changed in every second instance that
     has a crashed process: one of them crashes in round 0 instead and reaches nobody. Every
     fourth instance otherwise just names a crashed process. Returns the pid per instance (-1: none):
     extreme_rows puts INT32_MIN there, so the minimum is lost, or spreads only as far as the
@@ -473,11 +458,11 @@ def explicit_inputs(name, n):
             ho, crash = S.random_omission(rng, I, R, n, 255 / 256), None
             init = (rng.random((I, n)) >= 0.5 / n).astype(np.int32)
         else:
-            ho, crash = _schedule(rng, alg, n, R, I, family)
+            ho, crash = random_schedule(rng, alg, n, R, I, family)
             if crash is not None and not (crash[:, lo:] >= 0).any():
                 continue
             min_at = None if crash is None else silence_some_crashed(ho, crash, n)
-            init = extreme_rows(rng, I, n, min_at) if name in EXTREME_ALGS else _init(rng, alg, I, n, 4)
+            init = extreme_rows(rng, I, n, min_at) if name in EXTREME_ALGS else random_init(rng, alg, I, n, 4)
         return Explicit(alg, R, I, ho, crash, init)
     raise AssertionError(f"{name}-n{n}: no schedule of the sequence crashes a process of the last mask word")
 
@@ -519,11 +504,6 @@ def check_extreme_rows(name, n):
         assert set(row.tolist()) <= set(EXTREMES) | set(POOL)
 
 
-def _np_inst_tuple(a):
-    return (int(a["digest"]), tuple(int(v) for v in a["first_fail"]), int(a["term_round"]), int(a["n_checks"]),
-            int(a["n_decided"]))
-
-
 @gpu
 @pytest.mark.parametrize("name,n", EXPLICIT_CASES, ids=_ids(EXPLICIT_CASES))
 def test_explicit_matches_oracle(name, n, oracle_mod):
@@ -547,18 +527,17 @@ def test_explicit_matches_oracle(name, n, oracle_mod):
         s, pi = ctx.run_batch_np(BEGIN, x.I)
         dec, dr = ctx.copy_decisions_np()
         fs, fr = ctx.fetch_np(ids)
-    _cmp_summary(s, o.osum, x.R)
-    mism = [i for i in range(x.I) if _np_inst_tuple(pi[i]) != _inst_tuple(o.opi[i])]
-    assert not mism, f"{len(mism)} instance summaries differ, first {mism[:5]}"
+    cmp_summary(s, o.osum, x.R)
+    cmp_instances(pi, o.opi)
     assert (dr == o.dround).all()
     if name == "eps":
         assert np.allclose(dec, o.dec, atol=F64_ABS_TOL, rtol=0, equal_nan=True)
     else:
         assert (dec == o.dec).all()
-    orr = np.array([_rec_tuple(r) for r in o.orec], np.int64).reshape(x.I, n, 4)
+    orr = np.array([rec_tuple(r) for r in o.orec], np.int64).reshape(x.I, n, 4)
     for j, inst in enumerate(ids):
         i = inst - BEGIN
-        assert _np_inst_tuple(fs[j]) == _inst_tuple(o.opi[i]), inst
+        assert np_inst_tuple(fs[j]) == inst_tuple(o.opi[i]), inst
         fields = ("decision_round", "halt_round") if name == "eps" else ("decision", "decision_round", "halt_round",
                                                                           "final_x")
         cols = (1, 2) if name == "eps" else (0, 1, 2, 3)
@@ -567,15 +546,6 @@ def test_explicit_matches_oracle(name, n, oracle_mod):
 
 
 # ------------------------------------------------------------------------------------ fused modules
-def fused_modules():
-    """(algorithm, n) of every fused module the tests below load (scripts/precompile_specs.py)."""
-    return sorted({(ROW[row].alg, n) for row, n in FUSED + FUSED_X})
-
-
-def _fused_rows(pi, k):
-    return [(tuple(s.first_fail)[:k], s.term_round, s.digest) for s in pi]
-
-
 def _assert_fused_equals_traced(gr, cnt, alg, n):
     """One context: the interpreter over the traced run, then the fused module's round kernel."""
     prog = traced_program(alg, n)
@@ -584,7 +554,7 @@ def _assert_fused_equals_traced(gr, cnt, alg, n):
     k = len(prog.slot_names)
     tr = gr.run_spec(BEGIN, cnt, prog, per_instance=True)
     fu = gr.run_spec(BEGIN, cnt, fused, per_instance=True)
-    assert _fused_rows(fu.per_instance, k) == _fused_rows(tr.per_instance, k)
+    assert spec_rows(fu.per_instance, k, digest=True) == spec_rows(tr.per_instance, k, digest=True)
     assert list(fu.summary.fail_count)[:k] == list(tr.summary.fail_count)[:k]
     assert (fu.summary.digest, fu.summary.decided_processes) == (tr.summary.digest, tr.summary.decided_processes)
     return tr

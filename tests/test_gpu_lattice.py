@@ -1,80 +1,25 @@
 """GPU: LatticeAgreement (psg_lattice.hip) against the pure-Python restatement of the reference.
 
 The oracle library has no LatticeAgreement, so the reference side is `py_lattice`
-(tests/test_reference_lattice.py, written from example/LatticeAgreement.scala). Explicit and
+(tests/restatement.py, written from example/LatticeAgreement.scala). Explicit and
 seeded schedules, hand KATs, sharding and fetch, a custom Spec in its three forms, the adversary.
 """
-import ctypes as C
 import functools
 
 import numpy as np
 import pytest
 
 from round_amd import abi, adversary as A, formula as F, psync, records, schedules as S
-from round_amd.formula import P, init, old
 
-from test_reference_lattice import KAT_IDS, KATS, LATTICE, NEVER, ho_ints, kat_mutant_n5, py_lattice
+import spec_cases
+from gpu_support import (assert_equal_to_restatement, assert_multi_device_equals_one_device, gpu_explicit, seeded_inits,
+                         sharding_and_fetch)
+from restatement import (LATTICE_KAT_IDS, LATTICE_KATS, M64, NEVER, digest_of, ho_array, ho_ints, lattice_kat_mutant_n5,
+                         py_lattice)
 
 pytestmark = pytest.mark.gpu
-M64 = (1 << 64) - 1
+LATTICE = abi.PSG_ALG_LATTICE
 NS = [1, 2, 3, 5, 63, 64, 65, 128, 129, 192, 193, 256]  # every W and both sides of each wave edge
-
-
-def ho_array(hos, n):
-    """Python ints [I][R][n] -> uint64 [I][R][n][W]."""
-    W = (n + 63) // 64
-    out = np.zeros((len(hos), len(hos[0]), n, W), np.uint64)
-    for i, h in enumerate(hos):
-        for k, row in enumerate(h):
-            for p, m in enumerate(row):
-                for w in range(W):
-                    out[i, k, p, w] = (m >> (64 * w)) & M64
-    return out
-
-
-def _splitmix64(x):
-    x = (x + 0x9E3779B97F4A7C15) & M64
-    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & M64
-    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & M64
-    return x ^ (x >> 31)
-
-
-def digest_of(run):
-    """The per-instance digest of a py_lattice run: decision, rounds, proposed."""
-    d = 0
-    for pid, (dec, dr, hr, x) in enumerate(run.rec):
-        y = (pid << 32) | ((dr & 0xFFFF) << 16) | (hr & 0xFFFF)
-        z = ((dec & 0xFFFFFFFF) << 32) | (x & 0xFFFFFFFF)
-        d = (d + _splitmix64(z ^ _splitmix64(y))) & M64
-    return d
-
-
-def gpu_explicit(alg, n, R, inits, ho, **kw):
-    """Run explicit schedules; returns (summary, per-instance summaries, decision, decision_round,
-    fetched summaries, fetched process records)."""
-    I = len(inits)
-    with psync.GpuRound(alg, n, R, batch_capacity=I, **kw) as g:
-        ctx = g._ctx
-        ctx.load_inputs(0, I, np.asarray(inits, np.int32))
-        ctx.load_schedule(0, I, ho, None)
-        s, pi = ctx.run_batch_np(0, I)
-        dec, dr = ctx.copy_decisions_np()
-        fs, fr = ctx.fetch_np(np.arange(I, dtype=np.uint64))
-    return s, pi, dec, dr, fs, fr
-
-
-def assert_equal_to_restatement(runs, pi, dec, dr, fs, fr):
-    for i, run in enumerate(runs):
-        assert [int(x) for x in dec[i]] == [r[0] for r in run.rec], i
-        assert [int(x) for x in dr[i]] == [r[1] for r in run.rec], i
-        assert [int(x) for x in fr[i]["halt_round"]] == [r[2] for r in run.rec], i
-        assert [int(x) for x in fr[i]["decision"]] == [r[0] for r in run.rec], i
-        assert [int(x) for x in fr[i]["decision_round"]] == [r[1] for r in run.rec], i
-        assert [int(x) for x in fr[i]["final_x"]] == [r[3] for r in run.rec], i
-        for s in (pi[i], fs[i]):
-            assert [int(x) for x in s["first_fail"][:6]] == run.first_fail, i
-            assert (int(s["term_round"]), int(s["n_decided"]), int(s["n_checks"])) == (run.term_round, run.n_decided, 6), i
-            assert int(s["digest"]) == digest_of(run), i
 
 
 def ending(run):
@@ -186,7 +131,7 @@ def test_the_cases_hold_every_ending():
 
 
 # ------------------------------------------------------------------------------------ 2. hand KATs
-@pytest.mark.parametrize("kat,variant,recs,ff,term,nd", KATS, ids=KAT_IDS)
+@pytest.mark.parametrize("kat,variant,recs,ff,term,nd", LATTICE_KATS, ids=LATTICE_KAT_IDS)
 def test_hand_kats_on_the_gpu(kat, variant, recs, ff, term, nd):
     n, inits, ho, R = kat()
     run = py_lattice(n, inits, ho, R, variant)
@@ -202,7 +147,7 @@ def test_hand_kats_on_the_gpu(kat, variant, recs, ff, term, nd):
 def test_mutant_kat_on_the_gpu():
     """Two disjoint quarters decide {0} and {1}: Comparability, Invariant0 and Safety first fail at
     check point 1 under variant 1; the reference algorithm decides nothing and holds."""
-    n, inits, ho, R = kat_mutant_n5()
+    n, inits, ho, R = lattice_kat_mutant_n5()
     hoa = ho_array([ho], n)
     s, pi, dec, dr, fs, fr = gpu_explicit(psync.LatticeAgreement(variant=1), n, R, [inits], hoa)
     assert [int(x) for x in pi[0]["first_fail"][:6]] == [1, 1, 1, NEVER, NEVER, NEVER]
@@ -213,20 +158,6 @@ def test_mutant_kat_on_the_gpu():
 
 
 # ------------------------------------------------------------------------------------ 3. seeded schedules
-def _seeded_inits(cfg, oracle_mod, begin, count):
-    """lattice_init(w, U) is a function of OTR's init value at value_range U * U: that value is
-    1 + mulhi32(w, U * U) with the same init word, so v = value - 1, elements v / U and v % U."""
-    U = cfg.value_range
-    c = abi.Config()
-    C.memmove(C.byref(c), C.byref(cfg), C.sizeof(abi.Config))
-    c.alg = abi.PSG_ALG_OTR
-    c.param = 2
-    c.value_range = U * U
-    v = np.array([[oracle_mod.init_value(c, begin + i, p) - 1 for p in range(cfg.n)] for i in range(count)], np.int64)
-    assert v.min() >= 0 and v.max() < U * U
-    return ((1 << (v // U)) | (1 << (v % U))).astype(np.int32)
-
-
 @pytest.mark.parametrize("n,drop,crash,U", [(5, 1, None, 16), (5, 2, None, 3), (64, 2, None, 16), (64, 2, 31, 16),
                                            (100, 1, None, 31), (256, 2, None, 16), (256, 1, None, 2)])
 def test_seeded_run_equals_the_restatement_on_its_materialized_schedule(n, drop, crash, U, oracle_mod):
@@ -242,7 +173,7 @@ def test_seeded_run_equals_the_restatement_on_its_materialized_schedule(n, drop,
         s, pi = ctx.run_batch_np(begin, cnt)
         dec, dr = ctx.copy_decisions_np()
         fs, fr = ctx.fetch_np(np.arange(begin, begin + cnt, dtype=np.uint64))
-        inits = _seeded_inits(cfg, oracle_mod, begin, cnt)
+        inits = seeded_inits(cfg, oracle_mod, begin, cnt)
         runs = [py_lattice(n, inits[i], ho_ints(ho[i]), R) for i in range(cnt)]
         assert_equal_to_restatement(runs, pi, dec, dr, fs, fr)
         assert (cr == -1).all() if crash is None else (cr >= 0).any()
@@ -272,38 +203,12 @@ def test_seeded_run_equals_the_restatement_on_its_materialized_schedule(n, drop,
 # ------------------------------------------------------------------------------------ 4. sharding and fetch
 @pytest.mark.parametrize("n,cnt", [(64, 1), (64, 3), (5, 5), (64, 200), (130, 50)])
 def test_sharding_and_fetch_equal_one_range(n, cnt):
-    begin = 500
-    with psync.GpuRound(psync.LatticeAgreement(), n, rounds=4, seed=8, batch_capacity=cnt) as g:
-        ctx = g._ctx
-        s, pi = ctx.run_batch_np(begin, cnt)
-        dec, dr = ctx.copy_decisions_np()
-        a = cnt // 2
-        parts = [ctx.run_batch_np(begin, a), ctx.run_batch_np(begin + a, cnt - a)] if a else [ctx.run_batch_np(begin, cnt)]
-        assert np.concatenate([p[1] for p in parts]).tobytes() == pi.tobytes()
-        assert sum(p[0].digest for p in parts) & M64 == s.digest & M64
-        assert sum(p[0].decided_processes for p in parts) == s.decided_processes
-        ids = np.array(sorted({begin + (7 * j) % cnt for j in range(min(cnt, 9))}, reverse=True), np.uint64)
-        fs, fr = ctx.fetch_np(ids)
-        for j, i in enumerate(int(x) - begin for x in ids):
-            assert fs[j].tobytes() == pi[i].tobytes()
-            assert (fr[j]["decision"] == dec[i]).all() and (fr[j]["decision_round"] == dr[i]).all()
-            assert (fr[j]["halt_round"] == fr[j]["decision_round"]).all()
+    for rec in sharding_and_fetch(psync.LatticeAgreement(), n, cnt):
+        assert (rec["halt_round"] == rec["decision_round"]).all()
 
 
 def test_multi_device_context_equals_one_device():
-    """A device-list context ([0, 0]: two per-device contexts on the one card) gives the single
-    context's summary, per-instance summaries, decisions and fetched records."""
-    n, cnt, begin = 130, 201, 77
-    out = []
-    for devices in (None, [0, 0]):
-        with psync.GpuRound(psync.LatticeAgreement(), n, seed=6, batch_capacity=cnt, devices=devices) as g:
-            r = g.run(begin, cnt, per_instance=True)
-            f = g.fetch([begin, begin + 100, begin + cnt - 1])
-            out.append((abi.summary_to_list(r.summary)[:-1],
-                        [(s.digest, tuple(s.first_fail), s.term_round, s.n_decided) for s in r.per_instance],
-                        g.decisions(), [s.digest for s in f[0]],
-                        [(x.decision, x.decision_round, x.halt_round, x.final_x) for x in f[1]]))
-    assert out[0] == out[1]
+    assert_multi_device_equals_one_device(psync.LatticeAgreement())
 
 
 # ------------------------------------------------------------------------------------ 5. rounds past 64
@@ -336,22 +241,8 @@ def test_rounds_past_64_check_only_tail():
 
 
 # ------------------------------------------------------------------------------------ 6. generic Spec
-def custom_spec():
-    """A Spec on the existing operators (the Formula language has no set operators): a defined
-    decision equals proposed; proposed never falls below its initial value (a superset's mask is
-    never numerically smaller); Irrevocability; every live process hears more than 2n/3 (fails often)."""
-    return F.Spec(properties=[
-        ("Termination", P.forall(lambda i: i.decided)),
-        ("DecisionIsProposed", P.forall(lambda i: i.decided.implies(i.decision == i.x))),
-        ("Grows", P.forall(lambda i: i.x >= init(i.x))),
-        ("Irrevocability", P.forall(lambda i: old(i.decided).implies(i.decided & (old(i.decision) == i.decision)))),
-        ("HearsTwoThirds", P.forall(lambda i: i.HO.size > 2 * F.n // 3)),
-        ("OneSet", P.forall(lambda i: P.forall(lambda j: i.x == j.x))),
-    ])
-
-
 def spec_from_states(run):
-    """custom_spec's slots evaluated in Python from py_lattice's states."""
+    """spec_cases.lattice_custom's slots evaluated in Python from py_lattice's states."""
     ff, term = [NEVER] * 5, NEVER
     st = run.states
     for c, cur in enumerate(st):
@@ -379,7 +270,7 @@ def test_custom_spec_equals_the_restatement(n, mode):
     ho[1::3, 0] = S.full_mask(n)
     v = rng.integers(0, 16, (I, n))
     inits = ((1 << (v // 4)) | (1 << (v % 4))).astype(np.int32)
-    spec = custom_spec()
+    spec = spec_cases.lattice_custom()
     prog = F.compile_spec(spec, LATTICE) if mode == "vm" else F.compile_native(spec, LATTICE, fused=mode == "fused", n=n)
     with psync.GpuRound(psync.LatticeAgreement(), n, R, batch_capacity=I) as g:
         g._ctx.load_inputs(0, I, inits)

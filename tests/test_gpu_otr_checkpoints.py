@@ -1,6 +1,6 @@
 """OTR / OTR2 check points on the GPU: the settled fast path's per-lane record, the
 no-witness arm and the witness arm of otr_check (psg_otr.hip), bit-exact against the CPU
-oracle on (digest, first_fail[0..7], term_round, n_checks, n_decided) per instance and on
+oracle on (digest, first_fail, term_round, n_checks, n_decided) per instance and on
 the batch summary.
 
 A frozen check point sees the state of the last live check point before it, so it can never
@@ -14,30 +14,12 @@ import pytest
 
 from round_amd import abi, psync
 
+from gpu_support import cmp_instances, cmp_summary, inst_tuple, otr_alg
+
 pytestmark = pytest.mark.gpu
 
 H = psync.HOSchedule
 NEVER = 0xFF
-
-
-def _cmp_summary(g, o, rounds):
-    assert g.instances == o.instances
-    assert g.process_rounds == o.process_rounds
-    assert (g.active_process_rounds, g.live_instance_rounds) == (o.active_process_rounds, o.live_instance_rounds)
-    assert list(g.fail_count) == list(o.fail_count)
-    assert g.decided_processes == o.decided_processes
-    assert g.digest == o.digest
-    assert list(g.term_hist)[: rounds + 2] == list(o.term_hist)[: rounds + 2]
-
-
-def _inst_tuple(s):
-    return (s.digest, tuple(s.first_fail)[:8], s.term_round, s.n_checks, s.n_decided)
-
-
-def _cmp_instances(gpu_pi, opi):
-    mism = [i for i in range(len(opi)) if _inst_tuple(gpu_pi[i]) != _inst_tuple(opi[i])]
-    assert not mism, f"{len(mism)} instance summaries differ, first {mism[:5]}: " \
-                     f"{_inst_tuple(gpu_pi[mism[0]])} != {_inst_tuple(opi[mism[0]])}"
 
 
 # --------------------------------------------------------------------------- 1. exact threshold
@@ -69,7 +51,7 @@ def _reversed(n, init, ho):
 
 
 THRESHOLD_ROWS = [
-    # (id, algorithm, (n, ones, dev), first_fail[0..7], term_round)
+    # (id, algorithm, (n, ones, dev), first_fail, term_round)
     ("otr-n24", psync.OTR(variant=1), (24, 17, 9), [255, 2, 0, 0, 255, 255, 255, 255], 2),
     ("otr-n64-cnt42", psync.OTR(variant=1), (64, 43, 22), [255, 2, 0, 0, 255, 255, 255, 255], 2),  # cnt = 2n/3
     ("otr-n64-cnt43", psync.OTR(variant=1), (64, 43, 21), [255, 255, 0, 0, 255, 255, 255, 255], 2),  # holds
@@ -96,7 +78,7 @@ def test_first_failure_through_settled_path_at_threshold(cid, alg, shape, want_f
         assert list(s.first_fail)[:8] == want_ff and s.term_round == want_term
         x2, d2 = tr[2]
         assert all(d2) and sum(1 for v in x2 if v == 1) == n - dev  # settled at check point 2, cnt = n - dev
-    assert _inst_tuple(rows[0])[1:] == _inst_tuple(rows[1])[1:]  # OTR is symmetric in pids
+    assert inst_tuple(rows[0])[1:] == inst_tuple(rows[1])[1:]  # OTR is symmetric in pids
     slot1_fails = want_ff[1] != NEVER
     assert slot1_fails == (not isinstance(alg, psync.OTR2) and n - dev <= (2 * n) // 3)
     ho_np = np.array([ho, rho], dtype=np.uint64).reshape(2, R, n, 1)
@@ -106,17 +88,13 @@ def test_first_failure_through_settled_path_at_threshold(cid, alg, shape, want_f
         g.load_schedule(begin, 2, ho_np)
         res = g.run(begin, 2, per_instance=True)
     osum, opi, _, _, _ = oracle_mod.run_schedule(g.cfg, begin, 2, ho_np, None, init_np, per_instance=True)
-    assert [_inst_tuple(s)[1:] for s in opi] == [_inst_tuple(s)[1:] for s in rows]
-    _cmp_instances(res.per_instance, opi)
-    _cmp_summary(res.summary, osum, R)
+    assert [inst_tuple(s)[1:] for s in opi] == [inst_tuple(s)[1:] for s in rows]
+    cmp_instances(res.per_instance, opi)
+    cmp_summary(res.summary, osum, R)
 
 
 # --------------------------------------------------------------------------- 2. threshold shapes
 SHAPES = [(a, n, V) for a in ("otr", "otr2") for n in (1, 2, 3, 4, 5, 63, 64) for V in (1, 2, 64)]
-
-
-def _alg(name, **kw):
-    return (psync.OTR2 if name == "otr2" else psync.OTR)(**kw)
 
 
 def _no_late_failures(opi):
@@ -130,15 +108,15 @@ def test_threshold_shapes_seeded(name, n, V, oracle_mod):
     0 on the oracle, so any difference is a false failure from the per-lane thresholds or from
     lanes past n."""
     begin, count = 1000, 400
-    with psync.GpuRound(_alg(name), n, rounds=20, seed=11, value_range=V, batch_capacity=count) as g:
+    with psync.GpuRound(otr_alg(name), n, rounds=20, seed=11, value_range=V, batch_capacity=count) as g:
         res = g.run(begin, count, per_instance=True)
     osum, opi, _ = oracle_mod.run(g.cfg, begin, count, per_instance=True, threads=8)
     _no_late_failures(opi)
     if V == 1:  # every x is the same value from the start: OTR fails only Invariant2 (nobody decided yet)
         failing = [k for k in range(8) if osum.fail_count[k]]
         assert failing == ([] if name == "otr2" else [3])
-    _cmp_instances(res.per_instance, opi)
-    _cmp_summary(res.summary, osum, 20)
+    cmp_instances(res.per_instance, opi)
+    cmp_summary(res.summary, osum, 20)
 
 
 def test_threshold_shapes_max_rounds(oracle_mod):
@@ -148,8 +126,8 @@ def test_threshold_shapes_max_rounds(oracle_mod):
         res = g.run(begin, count, per_instance=True)
     osum, opi, _ = oracle_mod.run(g.cfg, begin, count, per_instance=True, threads=8)
     _no_late_failures(opi)
-    _cmp_instances(res.per_instance, opi)
-    _cmp_summary(res.summary, osum, R)
+    cmp_instances(res.per_instance, opi)
+    cmp_summary(res.summary, osum, R)
 
 
 # --------------------------------------------------------------------------- 3. witness arm
@@ -161,7 +139,7 @@ def test_witness_arm(name, oracle_mod):
     cannot fail with these inputs: every x, and so every decision, is some process's initial
     value. For OTR2 the oracle is the expectation, with no fixed counts."""
     begin, count = 1000, 3000
-    with psync.GpuRound(_alg(name, variant=1), 5, rounds=20, seed=7, value_range=3,
+    with psync.GpuRound(otr_alg(name, variant=1), 5, rounds=20, seed=7, value_range=3,
                         schedule=H(drop_log2=1, good_round=0.0), batch_capacity=count) as g:
         res = g.run(begin, count, per_instance=True)
     osum, opi, _ = oracle_mod.run(g.cfg, begin, count, per_instance=True, threads=8)
@@ -169,5 +147,5 @@ def test_witness_arm(name, oracle_mod):
         for k in (0, 1, 4, 6, 7):
             assert osum.fail_count[k] >= 1, f"slot {k} never fails on the oracle"
     assert osum.fail_count[5] == 0
-    _cmp_instances(res.per_instance, opi)
-    _cmp_summary(res.summary, osum, 20)
+    cmp_instances(res.per_instance, opi)
+    cmp_summary(res.summary, osum, 20)

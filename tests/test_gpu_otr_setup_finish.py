@@ -1,7 +1,7 @@
 """OTR / OTR2 per-instance setup and finish on the GPU (psg_otr.hip, W = 1): the X0 window
 test and its LDS bitmap (X0Set::build_window), check point 0 from the initial state
 (otr_check_initial), the summary record packed into one store and the per-wave counter sums
-(finish_instance_w1, WaveTally). Exact against the CPU oracle on (digest, first_fail[0..7],
+(finish_instance_w1, WaveTally). Exact against the CPU oracle on (digest, first_fail,
 term_round, n_checks, n_decided) per instance, on the decisions and on the batch summary.
 
 Every case first asserts, on its inputs and on the oracle's own output, that the regime it
@@ -12,30 +12,13 @@ import pytest
 
 from round_amd import psync
 
+from gpu_support import BEGIN, cmp_instances, cmp_summary, otr_alg
+
 pytestmark = pytest.mark.gpu
 
 H = psync.HOSchedule
 NEVER = 0xFF
 INT32_MIN = -(2 ** 31)
-BEGIN = 1000
-
-
-def _alg(name, **kw):
-    return (psync.OTR2 if name == "otr2" else psync.OTR)(**kw)
-
-
-def _inst_tuple(s):
-    return (s.digest, tuple(s.first_fail)[:8], s.term_round, s.n_checks, s.n_decided)
-
-
-def _cmp_summary(g, o, rounds):
-    assert g.instances == o.instances
-    assert g.process_rounds == o.process_rounds
-    assert (g.active_process_rounds, g.live_instance_rounds) == (o.active_process_rounds, o.live_instance_rounds)
-    assert list(g.fail_count) == list(o.fail_count)
-    assert g.decided_processes == o.decided_processes
-    assert g.digest == o.digest
-    assert list(g.term_hist)[: rounds + 2] == list(o.term_hist)[: rounds + 2]
 
 
 def _oracle(oracle_mod, cfg, count, init=None):
@@ -49,12 +32,10 @@ def _gpu_equals_oracle(alg, n, rounds, count, ora, init=None, **kw):
         g.load_inputs(BEGIN, count, init)
         res = g.run(BEGIN, count, per_instance=True)
         dec, dround = g.decisions()
-    mism = [i for i in range(count) if _inst_tuple(res.per_instance[i]) != _inst_tuple(opi[i])]
-    assert not mism, f"{len(mism)} instance summaries differ, first {mism[:5]}: " \
-                     f"{_inst_tuple(res.per_instance[mism[0]])} != {_inst_tuple(opi[mism[0]])}"
+    cmp_instances(res.per_instance, opi)
     assert list(dec) == [r.decision for r in orec]
     assert list(dround) == [r.decision_round for r in orec]
-    _cmp_summary(res.summary, osum, rounds)
+    cmp_summary(res.summary, osum, rounds)
 
 
 def _cfg(alg, n, rounds, **kw):
@@ -71,7 +52,7 @@ def test_seeded_shapes_default_schedule(name, n, oracle_mod):
     small and full waves. Slot 2 (Invariant1) fails at check point 0 wherever two processes start
     with different values, and Termination first holds at several different check points."""
     count, kw = 300, dict(seed=21, value_range=64)
-    ora = _oracle(oracle_mod, _cfg(_alg(name), n, 20, **kw), count)
+    ora = _oracle(oracle_mod, _cfg(otr_alg(name), n, 20, **kw), count)
     osum, opi, _ = ora
     assert H().good_round == 0.25 and H().drop_log2 == 3
     if n >= 2:
@@ -80,7 +61,7 @@ def test_seeded_shapes_default_schedule(name, n, oracle_mod):
         assert osum.fail_count[2] == 0  # one process: cnt == n
     if n >= 3:
         assert sum(1 for v in list(osum.term_hist)[:22] if v) >= 2
-    _gpu_equals_oracle(_alg(name), n, 20, count, ora, **kw)
+    _gpu_equals_oracle(otr_alg(name), n, 20, count, ora, **kw)
 
 
 # --------------------------------------------------------------------------- 2. X0 regimes
@@ -137,7 +118,7 @@ def test_host_initial_values_in_each_x0_regime(name, n, regime, oracle_mod):
         init = _regime_rows(regime, count, n, rng)
         assert _in_regime(regime, init)
     init = init.astype(np.int32)
-    ora = _oracle(oracle_mod, _cfg(_alg(name), n, 20, **kw), count, init=init.tolist())
+    ora = _oracle(oracle_mod, _cfg(otr_alg(name), n, 20, **kw), count, init=init.tolist())
     osum, opi, orec = ora
     if regime == "equal":
         # nobody differs: Invariant1 holds at check point 0; OTR fails only Invariant2 there
@@ -146,7 +127,7 @@ def test_host_initial_values_in_each_x0_regime(name, n, regime, oracle_mod):
     else:
         assert sum(1 for s in opi if s.first_fail[2] == 0) >= count // 2
     assert osum.decided_processes > 0 and osum.fail_count[5] == 0  # decisions are initial values
-    _gpu_equals_oracle(_alg(name), n, 20, count, ora, init=init, **kw)
+    _gpu_equals_oracle(otr_alg(name), n, 20, count, ora, init=init, **kw)
 
 
 def test_seeded_value_range_above_window(oracle_mod):
@@ -170,12 +151,12 @@ def test_every_round_good(name, oracle_mod):
     """good_round = 1.0 with drop_log2 = 3: every executed round reads the common HO set, round 0
     included, and every instance terminates at check point 2."""
     count, kw = 300, dict(seed=24, value_range=64, schedule=H(drop_log2=3, good_round=1.0, self_bit=False))
-    cfg = _cfg(_alg(name), 64, 20, **kw)
+    cfg = _cfg(otr_alg(name), 64, 20, **kw)
     good, total = _common_set_rounds(oracle_mod, cfg, 40)
     assert good == total
     ora = _oracle(oracle_mod, cfg, count)
     assert ora[0].term_hist[2] == count and ora[0].decided_processes == count * 64
-    _gpu_equals_oracle(_alg(name), 64, 20, count, ora, **kw)
+    _gpu_equals_oracle(otr_alg(name), 64, 20, count, ora, **kw)
 
 
 def test_no_round_good(oracle_mod):
@@ -198,7 +179,7 @@ def test_good_rounds_past_the_64_round_block(name, oracle_mod):
     (variant = 1) at n = 5 under heavy loss, where a fifth of the instances keeps an undecided
     process to the end."""
     n, R, count = 5, 70, 300
-    alg = _alg(name, variant=1)
+    alg = otr_alg(name, variant=1)
     kw = dict(seed=5, value_range=64, schedule=H(drop_log2=1, good_round=0.25))
     cfg = _cfg(alg, n, R, **kw)
     ora = _oracle(oracle_mod, cfg, count)

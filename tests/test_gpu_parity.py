@@ -9,6 +9,8 @@ import pytest
 
 from round_amd import abi, psync
 
+from gpu_support import check_eps, close, cmp_instances, cmp_summary, inst_tuple, rec_tuple
+
 pytestmark = pytest.mark.gpu
 
 H = psync.HOSchedule
@@ -119,24 +121,6 @@ CASES = [
 ]
 
 
-def _cmp_summary(g, o, rounds):
-    assert g.instances == o.instances
-    assert g.process_rounds == o.process_rounds
-    assert (g.active_process_rounds, g.live_instance_rounds) == (o.active_process_rounds, o.live_instance_rounds)
-    assert list(g.fail_count) == list(o.fail_count)
-    assert g.decided_processes == o.decided_processes
-    assert g.digest == o.digest
-    assert list(g.term_hist)[: rounds + 2] == list(o.term_hist)[: rounds + 2]
-
-
-def _inst_tuple(s):
-    return (s.digest, tuple(s.first_fail), s.term_round, s.n_checks, s.n_decided)
-
-
-def _rec_tuple(r):
-    return (r.decision, r.decision_round, r.halt_round, r.final_x)
-
-
 @pytest.mark.parametrize("cid,alg,n,count,kw", CASES, ids=[c[0] for c in CASES])
 def test_gpu_matches_oracle(cid, alg, n, count, kw, oracle_mod):
     begin = 1000  # non-zero instance ids
@@ -147,18 +131,17 @@ def test_gpu_matches_oracle(cid, alg, n, count, kw, oracle_mod):
         fsums, frecs = gr.fetch(sample)
     cfg = gr.cfg
     osum, opi, orec = oracle_mod.run(cfg, begin, count, per_instance=True, records=True, threads=8)
-    _cmp_summary(res.summary, osum, cfg.rounds)
-    mism = [i for i in range(count) if _inst_tuple(res.per_instance[i]) != _inst_tuple(opi[i])]
-    assert not mism, f"{len(mism)} instance summaries differ, first {mism[:5]}"
+    cmp_summary(res.summary, osum, cfg.rounds)
+    cmp_instances(res.per_instance, opi)
     for i in range(count):
         for p in range(n):
             r = orec[i * n + p]
             assert dec[i * n + p] == r.decision and dround[i * n + p] == r.decision_round, (i, p)
     for j, inst in enumerate(sample):
         i = inst - begin
-        assert _inst_tuple(fsums[j]) == _inst_tuple(opi[i])
+        assert inst_tuple(fsums[j]) == inst_tuple(opi[i])
         for p in range(n):
-            assert _rec_tuple(frecs[j * n + p]) == _rec_tuple(orec[i * n + p]), (inst, p)
+            assert rec_tuple(frecs[j * n + p]) == rec_tuple(orec[i * n + p]), (inst, p)
 
 
 def test_host_supplied_inputs(oracle_mod):
@@ -169,8 +152,8 @@ def test_host_supplied_inputs(oracle_mod):
         gr.load_inputs(50, count, init)
         res = gr.run(50, count, per_instance=True)
     osum, opi, _ = oracle_mod.run(gr.cfg, 50, count, init=init, per_instance=True)
-    _cmp_summary(res.summary, osum, gr.cfg.rounds)
-    assert [_inst_tuple(s) for s in res.per_instance] == [_inst_tuple(s) for s in opi]
+    cmp_summary(res.summary, osum, gr.cfg.rounds)
+    assert [inst_tuple(s) for s in res.per_instance] == [inst_tuple(s) for s in opi]
 
 
 @pytest.mark.parametrize("drop", [3, 5])
@@ -209,8 +192,8 @@ def test_otr_round0_value_classes(alg, n, drop, oracle_mod):
         gr.load_inputs(90, count, init)
         res = gr.run(90, count, per_instance=True)
     osum, opi, orec = oracle_mod.run(gr.cfg, 90, count, init=init, per_instance=True, records=True)
-    _cmp_summary(res.summary, osum, gr.cfg.rounds)
-    assert [_inst_tuple(s) for s in res.per_instance] == [_inst_tuple(s) for s in opi]
+    cmp_summary(res.summary, osum, gr.cfg.rounds)
+    assert [inst_tuple(s) for s in res.per_instance] == [inst_tuple(s) for s in opi]
     # the mmor path ran: most instances end with some x different from its initial value
     moved = sum(any(orec[i * n + p].final_x != init[i][p] for p in range(n)) for i in range(count))
     assert moved > count // 2, moved
@@ -229,8 +212,8 @@ def test_host_supplied_inputs_wide(alg, n, oracle_mod):
         gr.load_inputs(70, count, init)
         res = gr.run(70, count, per_instance=True)
     osum, opi, _ = oracle_mod.run(gr.cfg, 70, count, init=init, per_instance=True)
-    _cmp_summary(res.summary, osum, gr.cfg.rounds)
-    assert [_inst_tuple(s) for s in res.per_instance] == [_inst_tuple(s) for s in opi]
+    cmp_summary(res.summary, osum, gr.cfg.rounds)
+    assert [inst_tuple(s) for s in res.per_instance] == [inst_tuple(s) for s in opi]
 
 
 def test_sharding_invariance_and_determinism():
@@ -300,12 +283,7 @@ def test_gpu_map_head_matches_oracle(oracle_mod):
 
 
 # --------------------------------------------------------------------------- EpsilonConsensus (Double)
-# Values: every step is the same IEEE operation in the same order on both sides, so
-# the GPU reproduces the oracle bit for bit; the stated tolerance covers libm log()
-# differing by an ulp (which can move maxR only when r1 sits within an ulp of an
-# integer). Integer results (rounds, first failing check points) must match exactly.
-F64_ABS_TOL = 1e-12
-
+# The tolerance on its Double values is gpu_support.F64_ABS_TOL; integer results must match exactly.
 EPS_CASES = [
     ("eps-n7-f1", psync.EpsilonConsensus(1, 0.1), 7, 4000, dict(seed=60)),
     ("eps-n16-f2", psync.EpsilonConsensus(2, 1e-3), 16, 2000, dict(seed=61)),
@@ -327,28 +305,6 @@ EPS_CASES = [
 ]
 
 
-def _close(a, b, tol=F64_ABS_TOL):
-    import math
-    if math.isnan(a) or math.isnan(b):
-        return math.isnan(a) and math.isnan(b)
-    return abs(a - b) <= tol
-
-
-def _check_eps(gr, res, dec, dround, begin, count, init=None, oracle_mod=None):
-    n = gr.cfg.n
-    osum, opi, orec, odec, ofx = oracle_mod.run_real(gr.cfg, begin, count, init=init, per_instance=True,
-                                                     records=True, threads=8)
-    _cmp_summary(res.summary, osum, gr.cfg.rounds)
-    for i in range(count):
-        g, o = res.per_instance[i], opi[i]
-        assert (tuple(g.first_fail), g.term_round, g.n_decided) == (tuple(o.first_fail), o.term_round, o.n_decided), i
-        assert g.digest == o.digest, i
-    for c in range(count * n):
-        assert dround[c] == orec[c].decision_round, c
-        assert _close(dec[c], odec[c]), (c, dec[c], odec[c])
-    return opi, orec, odec, ofx
-
-
 @pytest.mark.parametrize("cid,alg,n,count,kw", EPS_CASES, ids=[c[0] for c in EPS_CASES])
 def test_gpu_epsilon_matches_oracle(cid, alg, n, count, kw, oracle_mod):
     begin = 777
@@ -357,13 +313,13 @@ def test_gpu_epsilon_matches_oracle(cid, alg, n, count, kw, oracle_mod):
         dec, dround = gr.decisions()
         sample = [begin + i for i in range(0, count, max(1, count // 23))]
         fsums, frecs, fdec, ffx = gr.fetch_real(sample)
-    opi, orec, odec, ofx = _check_eps(gr, res, dec, dround, begin, count, oracle_mod=oracle_mod)
+    opi, orec, odec, ofx = check_eps(gr, res, dec, dround, begin, count, oracle_mod=oracle_mod)
     for j, inst in enumerate(sample):
         i = inst - begin
-        assert _inst_tuple(fsums[j]) == _inst_tuple(opi[i])
+        assert inst_tuple(fsums[j]) == inst_tuple(opi[i])
         for p in range(n):
-            assert _rec_tuple(frecs[j * n + p]) == _rec_tuple(orec[i * n + p]), (inst, p)
-            assert _close(fdec[j * n + p], odec[i * n + p]) and _close(ffx[j * n + p], ofx[i * n + p]), (inst, p)
+            assert rec_tuple(frecs[j * n + p]) == rec_tuple(orec[i * n + p]), (inst, p)
+            assert close(fdec[j * n + p], odec[i * n + p]) and close(ffx[j * n + p], ofx[i * n + p]), (inst, p)
 
 
 @pytest.mark.parametrize("n,f,dup", [(16, 2, 0.3), (33, 3, 0.6), (64, 5, 0.9)])
@@ -381,7 +337,7 @@ def test_gpu_epsilon_host_inputs(n, f, dup, oracle_mod):
         gr.load_inputs(5, count, init)
         res = gr.run(5, count, per_instance=True)
         dec, dround = gr.decisions()
-    _check_eps(gr, res, dec, dround, 5, count, init=init, oracle_mod=oracle_mod)
+    check_eps(gr, res, dec, dround, 5, count, init=init, oracle_mod=oracle_mod)
 
 
 @pytest.mark.gpu
@@ -407,4 +363,4 @@ def test_gpu_epsilon_keys_within_64_ulp_against_pid_order(n, f, oracle_mod):
         gr.load_inputs(0, count, init)
         res = gr.run(0, count, per_instance=True)
         dec, dround = gr.decisions()
-    _check_eps(gr, res, dec, dround, 0, count, init=init, oracle_mod=oracle_mod)
+    check_eps(gr, res, dec, dround, 0, count, init=init, oracle_mod=oracle_mod)

@@ -25,22 +25,18 @@ lv-n3-V5 alone (one misdrawn HO(coord), at k = 128, changes an n = 64 run only i
 would have succeeded). A refill that stays wrong after its first round is seen by every later
 decision; the parity modules that existed before pass under both builds.
 """
-import ctypes as C
-
 import numpy as np
 import pytest
 
 from round_amd import abi, formula as F, psync, schedules as S
 
 import spec_cases
-from test_gpu_parity import _check_eps, _cmp_summary, _inst_tuple, _rec_tuple
-from test_gpu_tpc import _outcomes, _seeded_votes, assert_equal_to_restatement, digest_of
-from test_reference_tpc import ho_ints, py_tpc
+from gpu_support import (BEGIN, assert_run_equals_oracle, cmp_instances, cmp_summary, rec_tuple, run_any, spec_rows,
+                         tpc_seeded)
+from restatement import tpc_outcomes
 
 gpu = pytest.mark.gpu
 H = psync.HOSchedule
-M64 = (1 << 64) - 1
-BEGIN = 1000  # non-zero instance ids
 LOSSY = H(drop_log2=1, good_round=0.02)  # links lost w.p. 1/2: progress only in the rare good rounds
 
 
@@ -143,26 +139,6 @@ def fetch_sample(count, last):
     return sorted({BEGIN + i for i in range(0, count, max(1, count // 19))} | {BEGIN + int(np.argmax(last))})
 
 
-def assert_run_equals_oracle(gr, count, osum, opi, orec, sample):
-    """One GPU run of [BEGIN, BEGIN + count) against the oracle's results."""
-    n = gr.cfg.n
-    res = gr.run(BEGIN, count, per_instance=True)
-    dec, dround = gr.decisions()
-    fsums, frecs = gr.fetch(sample)
-    _cmp_summary(res.summary, osum, gr.cfg.rounds)
-    mism = [i for i in range(count) if _inst_tuple(res.per_instance[i]) != _inst_tuple(opi[i])]
-    assert not mism, f"{len(mism)} instance summaries differ, first {mism[:5]}"
-    odec = np.array([(r.decision, r.decision_round) for r in orec], np.int64)
-    bad = np.nonzero((np.array(dec, np.int64) != odec[:, 0]) | (np.array(dround, np.int64) != odec[:, 1]))[0]
-    assert bad.size == 0, f"decisions differ, first (instance, process) {divmod(int(bad[0]), n)}"
-    for j, inst in enumerate(sample):
-        i = inst - BEGIN
-        assert _inst_tuple(fsums[j]) == _inst_tuple(opi[i]), inst
-        for p in range(n):
-            assert _rec_tuple(frecs[j * n + p]) == _rec_tuple(orec[i * n + p]), (inst, p)
-    return res
-
-
 @gpu
 @pytest.mark.parametrize("cid", [c[0] for c in LONG])
 def test_long_live_run_matches_oracle(cid, oracle_mod):
@@ -191,30 +167,6 @@ FROZEN = [(f"{name}-n{n}-R{R}", alg, n, R, sched(n))
               ("eps", psync.EpsilonConsensus(5, 1e-300), (64, 100),
                lambda n: H(drop_log2=3, good_round=0.05, crash_fmax=5, ho_min=n - 6))]
           for n in ns for R in (70, 250)]
-
-
-def run_any(gr, oracle_mod, count, sample):
-    """One GPU run against a fresh oracle run of the same config (integer or Double algorithm)."""
-    n = gr.cfg.n
-    if not gr.alg.real:
-        osum, opi, orec = oracle_mod.run(gr.cfg, BEGIN, count, per_instance=True, records=True, threads=8)
-        assert_run_equals_oracle(gr, count, osum, opi, orec, sample)
-        return opi, orec
-    res = gr.run(BEGIN, count, per_instance=True)
-    dec, dround = gr.decisions()
-    fsums, frecs, fdec, ffx = gr.fetch_real(sample)
-    opi, orec, odec, ofx = _check_eps(gr, res, dec, dround, BEGIN, count, oracle_mod=oracle_mod)
-    assert [_inst_tuple(s) for s in res.per_instance] == [_inst_tuple(s) for s in opi]
-    as_bits = lambda xs: np.array(xs, np.float64).view(np.uint64)  # noqa: E731
-    assert (as_bits(dec) == as_bits(odec)).all()
-    for j, inst in enumerate(sample):
-        i = inst - BEGIN
-        assert _inst_tuple(fsums[j]) == _inst_tuple(opi[i]), inst
-        assert ([_rec_tuple(r) for r in frecs[j * n:(j + 1) * n]]
-                == [_rec_tuple(r) for r in orec[i * n:(i + 1) * n]]), inst
-        assert (as_bits(fdec[j * n:(j + 1) * n]) == as_bits(odec[i * n:(i + 1) * n])).all(), inst
-        assert (as_bits(ffx[j * n:(j + 1) * n]) == as_bits(ofx[i * n:(i + 1) * n])).all(), inst
-    return opi, orec
 
 
 @gpu
@@ -252,9 +204,8 @@ def test_long_live_run_under_a_spec_program(cid, mode, oracle_mod):
     with psync.GpuRound(alg, n, R, batch_capacity=count, **kw) as gr:
         built = gr.run(BEGIN, count, per_instance=True)
         sp = gr.run_spec(BEGIN, count, prog, per_instance=True)
-    assert [_inst_tuple(s) for s in built.per_instance] == [_inst_tuple(s) for s in opi]
-    rows = lambda pi: [(tuple(s.first_fail)[:k], s.term_round, s.digest) for s in pi]  # noqa: E731
-    assert rows(sp.per_instance) == rows(built.per_instance)
+    cmp_instances(built.per_instance, opi)
+    assert spec_rows(sp.per_instance, k, digest=True) == spec_rows(built.per_instance, k, digest=True)
     assert list(sp.summary.fail_count)[:k] == list(built.summary.fail_count)[:k]
     if mode.endswith("-ho"):  # |HO(p)| <= n holds at every check point
         assert all(s.first_fail[len(prog.slot_names) - 1] == abi.PSG_NEVER for s in sp.per_instance)
@@ -296,39 +247,6 @@ def test_round_count_edges_match_oracle(cid, alg, n, R, oracle_mod):
     if alg.alg_id == abi.PSG_ALG_FLOODMIN:  # decides in round k = f + 1 only
         assert {r.decision_round for r in orec} <= {-1, alg.param + 1}
         assert any(r.decision_round >= 0 for r in orec) == (R >= alg.param + 2)
-
-
-def schedule_cfg(cfg):
-    """The config under an algorithm the oracle library has: the schedule generator reads n, R,
-    the seed and the schedule parameters only (as _seeded_votes does for the init words)."""
-    c = abi.Config()
-    C.memmove(C.byref(c), C.byref(cfg), C.sizeof(abi.Config))
-    c.alg, c.param = abi.PSG_ALG_OTR, 2
-    return c
-
-
-def tpc_seeded(n, R, coord, sched, cnt, seed, oracle_mod):
-    """A seeded TwoPhaseCommit run == py_tpc on the schedule the library exports, and that schedule
-    == the oracle's restatement of the generator. Returns (runs, crash rounds)."""
-    alg = psync.TwoPhaseCommit(coord=coord)
-    with psync.GpuRound(alg, n, R, seed=seed, schedule=sched, batch_capacity=cnt) as g:
-        ctx = g._ctx
-        ho, cr = g.materialize_schedule(BEGIN, cnt)
-        s, pi = ctx.run_batch_np(BEGIN, cnt)
-        dec, dr = ctx.copy_decisions_np()
-        fs, fr = ctx.fetch_np(np.arange(BEGIN, BEGIN + cnt, dtype=np.uint64))
-        votes = _seeded_votes(g.cfg, oracle_mod, BEGIN, cnt)
-    oho, ocr = oracle_mod.materialize_schedule(schedule_cfg(g.cfg), BEGIN, cnt)
-    assert (ho == oho).all() and (cr == ocr).all()
-    runs = [py_tpc(n, coord, votes[i], ho_ints(ho[i]), R) for i in range(cnt)]
-    assert_equal_to_restatement(runs, pi, dec, dr, fs, fr)
-    assert s.decided_processes == sum(r.n_decided for r in runs)
-    assert s.digest & M64 == sum(digest_of(r) for r in runs) & M64
-    hist = [0] * (R + 2)
-    for r in runs:
-        hist[R + 1 if r.term_round == abi.PSG_NEVER else r.term_round] += 1
-    assert [s.term_hist[c] for c in range(R + 2)] == hist
-    return runs, cr
 
 
 @gpu
@@ -410,12 +328,9 @@ def test_coordinator_rotation_explicit_schedule(oracle_mod):
         fs, fr = ctx.fetch_np(np.arange(BEGIN, BEGIN + I, 15, dtype=np.uint64))
     osum, opi, orec, _, _ = oracle_mod.run_schedule(g.cfg, BEGIN, I, ho, None, init, per_instance=True, records=True)
     check_rotation_precondition(alg, n, orec, I)
-    _cmp_summary(s, osum, R)
-    for i in range(I):
-        a = pi[i]
-        assert (int(a["digest"]), tuple(int(x) for x in a["first_fail"]), int(a["term_round"]), int(a["n_checks"]),
-                int(a["n_decided"])) == _inst_tuple(opi[i]), i
-    orr = np.array([_rec_tuple(r) for r in orec], np.int64).reshape(I, n, 4)
+    cmp_summary(s, osum, R)
+    cmp_instances(pi, opi)
+    orr = np.array([rec_tuple(r) for r in orec], np.int64).reshape(I, n, 4)
     assert (dec == orr[:, :, 0]).all() and (dr == orr[:, :, 1]).all()
     for j, i in enumerate(range(0, I, 15)):
         assert int(fs[j]["digest"]) == opi[i].digest
@@ -456,7 +371,7 @@ def test_tpc_seeded_families_equal_the_restatement(cid, family, n, R, oracle_mod
     sched = dict(TPC_FAMILIES)[family](n)
     cnt = 64 if n <= 130 else 32
     runs, cr = tpc_seeded(n, R, n - 1, sched, cnt, 7, oracle_mod)
-    assert _outcomes(runs) == tpc_expected_outcomes(family, n)
+    assert tpc_outcomes(runs) == tpc_expected_outcomes(family, n)
     if family in ("crash", "crashall"):
         assert (cr[:, n - 1] >= 0).any(), "the coordinator crashes in no instance"
     else:  # at most 2 crashes among n: some process crashes, rarely the coordinator

@@ -8,11 +8,14 @@ the GPU equal the oracle's restatement of the generator word for word, and
 replaying them as explicit schedules reproduces the seeded run.
 """
 import os
+import zlib
 
 import numpy as np
 import pytest
 
 from round_amd import abi, adversary as A, lib, psync, records, schedules as S
+
+from gpu_support import cmp_instances, random_init, random_schedule
 
 pytestmark = pytest.mark.gpu
 
@@ -36,44 +39,13 @@ ALGS = [
 ]
 
 
-def _schedule(rng, alg, n, R, I, family):
-    if family == "crash":
-        fmax = max(1, alg.param)
-        crash, partial = S.random_crash(rng, I, R, n, fmax, p_partial=(0.1, 0.5, 0.9))
-        ho = S.crash_to_ho(crash, partial, R, n)
-        # a little benign loss on top, so explicit sets are not crash patterns only
-        ho &= ~(S.random_bits(rng, ho.shape, 1 / 64) & ~S.self_mask(n)[None, None])
-        return ho, crash
-    ho = S.random_omission(rng, I, R, n, 0.8)
-    if alg.alg_id == abi.PSG_ALG_BENOR:
-        S.repair_min_size(ho, rng, n, n // 2 + 1)
-    if alg.alg_id == abi.PSG_ALG_EPSILON:
-        S.repair_min_size(ho, rng, n, n - alg.param)
-    return ho, None
-
-
-def _init(rng, alg, I, n, V):
-    if alg.real:
-        return rng.random((I, n))
-    if alg.alg_id == abi.PSG_ALG_BENOR:
-        return rng.integers(0, 2, (I, n), dtype=np.int32)
-    return rng.integers(1, V + 1, (I, n), dtype=np.int32)
-
-
-def _cmp_summaries(gpu_pi, opi, k):
-    for j, (a, b) in enumerate(zip(gpu_pi, opi)):
-        assert int(a["digest"]) == b.digest, f"instance {j}: digest"
-        assert list(a["first_fail"][:k]) == list(b.first_fail)[:k], f"instance {j}: first_fail"
-        assert int(a["term_round"]) == b.term_round, f"instance {j}: term_round"
-
-
 @pytest.mark.parametrize("name,alg,n,R,V,family", ALGS, ids=[a[0] for a in ALGS])
 def test_explicit_schedule_matches_oracle(name, alg, n, R, V, family, oracle_mod):
-    rng = np.random.default_rng(abs(hash(name)) % 2 ** 32)
+    rng = np.random.default_rng(zlib.crc32(name.encode()))
     I = 300 if n <= 64 else 80
     begin = 1000
-    ho, crash = _schedule(rng, alg, n, R, I, family)
-    init = _init(rng, alg, I, n, V)
+    ho, crash = random_schedule(rng, alg, n, R, I, family)
+    init = random_init(rng, alg, I, n, V)
     with psync.GpuRound(alg, n, R, seed=5, value_range=max(V, 1), batch_capacity=I) as g:
         ctx = g._ctx
         ctx.load_inputs(begin, I, init)
@@ -85,8 +57,7 @@ def test_explicit_schedule_matches_oracle(name, alg, n, R, V, family, oracle_mod
         fs, fr = ctx.fetch_np(ids)
     osum, opi, orec, odec, _ = oracle_mod.run_schedule(g.cfg, begin, I, ho, crash, init, per_instance=True,
                                                         records=True)
-    k = len(alg.check_names)
-    _cmp_summaries(pi, opi, k)
+    cmp_instances(pi, opi)
     assert list(s.fail_count) == list(osum.fail_count)
     assert s.digest == osum.digest
     assert list(s.term_hist)[:R + 2] == list(osum.term_hist)[:R + 2]

@@ -12,26 +12,10 @@ import pytest
 from round_amd import abi, formula as F, psync
 
 import spec_cases
+from gpu_support import spec_rows
+from spec_cases import REF
 
 pytestmark = pytest.mark.gpu
-H = psync.HOSchedule
-
-REF = [
-    ("otr-n64", psync.OTR(), 64, 600, dict(value_range=8, seed=3)),
-    ("otr-mutant-n8", psync.OTR(variant=1), 8, 2000, dict(schedule=H(drop_log2=1, good_round=0.0), seed=4)),
-    ("otr-n100-W2", psync.OTR(), 100, 100, dict(value_range=4, seed=5)),
-    ("otr2-n64", psync.OTR2(), 64, 500, dict(value_range=4, seed=6)),
-    ("lv-n16-loss", psync.LastVoting(), 16, 500, dict(value_range=3, seed=7, schedule=H(
-        drop_log2=1, good_round=0.0, crash_fmax=7))),
-    ("lv-mutant-n6", psync.LastVoting(variant=1), 6, 1500, dict(value_range=5, seed=8)),
-    ("lv-n64", psync.LastVoting(), 64, 200, dict(seed=9, rounds=12)),
-    ("benor-n8", psync.BenOr(), 8, 1500, dict(seed=10)),
-    ("benor-n128-W2", psync.BenOr(), 128, 40, dict(seed=11, rounds=16)),
-]
-
-
-def _rows(pi, k):
-    return [(tuple(s.first_fail)[:k], s.term_round) for s in pi]
 
 
 def _prog(spec, alg_id, mode, n=None):
@@ -48,7 +32,7 @@ def test_reference_spec_program_matches_builtin_checks(cid, alg, n, count, kw, m
     with psync.GpuRound(alg, n, batch_capacity=count, **kw) as gr:
         built = gr.run(0, count, per_instance=True)
         spec = gr.run_spec(0, count, prog, per_instance=True)
-    assert _rows(spec.per_instance, k) == _rows(built.per_instance, k)
+    assert spec_rows(spec.per_instance, k) == spec_rows(built.per_instance, k)
     assert [s.digest for s in spec.per_instance] == [s.digest for s in built.per_instance]
     assert list(spec.summary.fail_count)[:k] == list(built.summary.fail_count)[:k]
     assert spec.summary.digest == built.summary.digest
@@ -65,7 +49,7 @@ def test_custom_spec_matches_cpu_interpreter(cid, alg, n, kw, mk, oracle_mod, mo
     tr = oracle_mod.trace(cfg, 100, count)
     ff, tm = oracle_mod.vm_run(prog, tr, count, n, cfg.rounds)
     k = len(prog.slot_names)
-    got = _rows(res.per_instance, k)
+    got = spec_rows(res.per_instance, k)
     assert got == [(tuple(f), t) for f, t in zip(ff, tm)]
     # counters agree with the per-instance view
     for s in range(k):
@@ -87,7 +71,7 @@ def test_spec_program_chunking_and_staged_inputs(oracle_mod, monkeypatch):
     cfg = gr.cfg
     tr = oracle_mod.trace(cfg, 0, count, init=init)
     ff, tm = oracle_mod.vm_run(prog, tr, count, n, cfg.rounds)
-    assert _rows(res.per_instance, len(prog.slot_names)) == [(tuple(f), t) for f, t in zip(ff, tm)]
+    assert spec_rows(res.per_instance, len(prog.slot_names)) == [(tuple(f), t) for f, t in zip(ff, tm)]
 
 
 def test_bad_program_is_rejected():

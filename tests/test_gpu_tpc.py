@@ -1,10 +1,9 @@
 """GPU: TwoPhaseCommit (psg_tpc.hip) against the pure-Python restatement of the reference.
 
 The oracle library has no TwoPhaseCommit, so the reference side is `py_tpc`
-(tests/test_reference_tpc.py, written from example/TwoPhaseCommit.scala). Explicit and seeded
+(tests/restatement.py, written from example/TwoPhaseCommit.scala). Explicit and seeded
 schedules, hand KATs, sharding and fetch, the generic Spec in its three forms, the adversary.
 """
-import ctypes as C
 import functools
 
 import numpy as np
@@ -12,68 +11,13 @@ import pytest
 
 from round_amd import abi, adversary as A, formula as F, psync, records, schedules as S
 
-from test_reference_tpc import (KATS, NEVER, NONE32, TPC, ho_ints, kat_coord_crashed_from_round2, kat_mutant_n5,
-                                py_tpc)
+from gpu_support import (assert_equal_to_restatement, assert_multi_device_equals_one_device, gpu_explicit, seeded_votes,
+                         sharding_and_fetch, spec_rows)
+from restatement import (M64, NEVER, NONE32, TPC_KAT_IDS, TPC_KATS, digest_of, ho_array, ho_ints, py_tpc,
+                         tpc_kat_coord_crashed_from_round2, tpc_kat_mutant_n5, tpc_outcomes)
 
 pytestmark = pytest.mark.gpu
-M64 = (1 << 64) - 1
-
-
-def ho_array(hos, n):
-    """Python ints [I][R][n] -> uint64 [I][R][n][W]."""
-    W = (n + 63) // 64
-    out = np.zeros((len(hos), len(hos[0]), n, W), np.uint64)
-    for i, h in enumerate(hos):
-        for k, row in enumerate(h):
-            for p, m in enumerate(row):
-                for w in range(W):
-                    out[i, k, p, w] = (m >> (64 * w)) & M64
-    return out
-
-
-def _splitmix64(x):
-    x = (x + 0x9E3779B97F4A7C15) & M64
-    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & M64
-    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & M64
-    return x ^ (x >> 31)
-
-
-def digest_of(run):
-    """The per-instance digest of a py_tpc run: callback value, rounds, vote."""
-    d = 0
-    for pid, (dec, dr, hr, vote) in enumerate(run.rec):
-        y = (pid << 32) | ((dr & 0xFFFF) << 16) | (hr & 0xFFFF)
-        z = ((dec & 0xFFFFFFFF) << 32) | (vote & 0xFFFFFFFF)
-        d = (d + _splitmix64(z ^ _splitmix64(y))) & M64
-    return d
-
-
-def gpu_explicit(alg, n, R, votes, ho, **kw):
-    """Run explicit schedules; returns (summary, per-instance summaries, decision, decision_round,
-    fetched summaries, fetched process records)."""
-    I = len(votes)
-    with psync.GpuRound(alg, n, R, batch_capacity=I, **kw) as g:
-        ctx = g._ctx
-        ctx.load_inputs(0, I, np.asarray(votes, np.int32))
-        ctx.load_schedule(0, I, ho, None)
-        s, pi = ctx.run_batch_np(0, I)
-        dec, dr = ctx.copy_decisions_np()
-        fs, fr = ctx.fetch_np(np.arange(I, dtype=np.uint64))
-    return s, pi, dec, dr, fs, fr
-
-
-def assert_equal_to_restatement(runs, pi, dec, dr, fs, fr):
-    for i, run in enumerate(runs):
-        assert [int(x) for x in dec[i]] == [r[0] for r in run.rec], i
-        assert [int(x) for x in dr[i]] == [r[1] for r in run.rec], i
-        assert [int(x) for x in fr[i]["halt_round"]] == [r[2] for r in run.rec], i
-        assert [int(x) for x in fr[i]["decision"]] == [r[0] for r in run.rec], i
-        assert [int(x) for x in fr[i]["decision_round"]] == [r[1] for r in run.rec], i
-        assert [int(x) for x in fr[i]["final_x"]] == [r[3] for r in run.rec], i
-        for s in (pi[i], fs[i]):
-            assert [int(x) for x in s["first_fail"][:4]] == run.first_fail, i
-            assert (int(s["term_round"]), int(s["n_decided"]), int(s["n_checks"])) == (run.term_round, run.n_decided, 4), i
-            assert int(s["digest"]) == digest_of(run), i
+TPC = abi.PSG_ALG_TPC
 
 
 # ------------------------------------------------------------------------------------ 1. explicit schedules
@@ -100,29 +44,16 @@ def _explicit_inputs(n, coord, R, self_bit):
         ho = S.random_omission(rng, 64, R, n, keep, self_bit)
         votes = (rng.random((64, n)) >= 0.5 / n).astype(np.int32)
         runs = [py_tpc(n, coord, votes[i], ho_ints(ho[i]), R) for i in range(64)]
-        if n < 3 or R < 3 or _outcomes(runs) == {"commit", "abort", "suspect"}:
+        if n < 3 or R < 3 or tpc_outcomes(runs) == {"commit", "abort", "suspect"}:
             return ho, votes, runs
     raise AssertionError("no seed of the sequence gives all three outcomes")
-
-
-def _outcomes(runs):
-    got = set()
-    for run in runs:
-        decs = [r[0] for r in run.rec]
-        if all(d == 1 for d in decs):
-            got.add("commit")
-        if any(d == 0 for d in decs):
-            got.add("abort")
-        if any(d == NONE32 for d in decs):
-            got.add("suspect")
-    return got
 
 
 @pytest.mark.parametrize("n,coord,R,self_bit", _cases())
 def test_explicit_schedules_equal_the_restatement(n, coord, R, self_bit):
     ho, votes, runs = _explicit_inputs(n, coord, R, self_bit)
     if n >= 3 and R >= 3:
-        assert _outcomes(runs) == {"commit", "abort", "suspect"}
+        assert tpc_outcomes(runs) == {"commit", "abort", "suspect"}
     s, pi, dec, dr, fs, fr = gpu_explicit(psync.TwoPhaseCommit(coord=coord), n, R, votes, ho)
     assert_equal_to_restatement(runs, pi, dec, dr, fs, fr)
     assert s.decided_processes == sum(r.n_decided for r in runs)
@@ -130,7 +61,7 @@ def test_explicit_schedules_equal_the_restatement(n, coord, R, self_bit):
 
 
 # ------------------------------------------------------------------------------------ 2. hand KATs
-@pytest.mark.parametrize("kat,recs,ff,term,nd", KATS, ids=[k[0].__name__ for k in KATS])
+@pytest.mark.parametrize("kat,recs,ff,term,nd", TPC_KATS, ids=TPC_KAT_IDS)
 def test_hand_kats_on_the_gpu(kat, recs, ff, term, nd):
     n, coord, votes, ho, R = kat()
     run = py_tpc(n, coord, votes, ho, R)
@@ -143,7 +74,7 @@ def test_hand_kats_on_the_gpu(kat, recs, ff, term, nd):
 def test_mutant_kat_on_the_gpu():
     """A no-voter's slot-1 link to the coordinator is dropped: the mutant commits, Validity and
     Safety first fail at check point 2; the reference algorithm aborts with no violation."""
-    n, coord, votes, ho, R = kat_mutant_n5()
+    n, coord, votes, ho, R = tpc_kat_mutant_n5()
     hoa = ho_array([ho], n)
     s, pi, dec, dr, fs, fr = gpu_explicit(psync.TwoPhaseCommit(coord=coord, variant=1), n, R, [votes], hoa)
     assert [int(x) for x in pi[0]["first_fail"][:4]] == [2, 2, NEVER, 2]
@@ -155,24 +86,13 @@ def test_mutant_kat_on_the_gpu():
 
 
 def test_crashed_coordinator_is_suspected():
-    n, coord, votes, ho, R = kat_coord_crashed_from_round2()
+    n, coord, votes, ho, R = tpc_kat_coord_crashed_from_round2()
     s, pi, dec, dr, fs, fr = gpu_explicit(psync.TwoPhaseCommit(coord=coord), n, R, [votes], ho_array([ho], n))
     assert [int(x) for x in dec[0][1:]] == [NONE32] * (n - 1) and [int(x) for x in dr[0][1:]] == [-1] * (n - 1)
     assert int(pi[0]["n_decided"]) == 1 and int(pi[0]["term_round"]) == NEVER
 
 
 # ------------------------------------------------------------------------------------ 3. seeded schedules
-def _seeded_votes(cfg, oracle_mod, begin, count):
-    """canCommit = (1 + mulhi32(w, V)) != 1 with the init word of every other algorithm: the
-    oracle's init value for the same seed and value_range under OTR's rule."""
-    c = abi.Config()
-    C.memmove(C.byref(c), C.byref(cfg), C.sizeof(abi.Config))
-    c.alg = abi.PSG_ALG_OTR
-    c.param = 2
-    return np.array([[int(oracle_mod.init_value(c, begin + i, p) != 1) for p in range(cfg.n)] for i in range(count)],
-                    np.int32)
-
-
 @pytest.mark.parametrize("n", [5, 64, 100, 256])
 def test_seeded_run_equals_the_restatement_on_its_materialized_schedule(n, oracle_mod):
     cnt, begin = 96, 1000
@@ -184,7 +104,7 @@ def test_seeded_run_equals_the_restatement_on_its_materialized_schedule(n, oracl
         s, pi = ctx.run_batch_np(begin, cnt)
         dec, dr = ctx.copy_decisions_np()
         fs, fr = ctx.fetch_np(np.arange(begin, begin + cnt, dtype=np.uint64))
-        votes = _seeded_votes(cfg, oracle_mod, begin, cnt)
+        votes = seeded_votes(cfg, oracle_mod, begin, cnt)
         runs = [py_tpc(n, alg.param, votes[i], ho_ints(ho[i]), cfg.rounds) for i in range(cnt)]
         assert_equal_to_restatement(runs, pi, dec, dr, fs, fr)
         assert (cr == -1).all()
@@ -210,38 +130,12 @@ def test_seeded_run_equals_the_restatement_on_its_materialized_schedule(n, oracl
 # ------------------------------------------------------------------------------------ 4. sharding and fetch
 @pytest.mark.parametrize("n,cnt", [(64, 1), (64, 3), (5, 5), (64, 200), (130, 50)])
 def test_sharding_and_fetch_equal_one_range(n, cnt):
-    begin = 500
-    with psync.GpuRound(psync.TwoPhaseCommit(), n, rounds=4, seed=8, batch_capacity=cnt) as g:
-        ctx = g._ctx
-        s, pi = ctx.run_batch_np(begin, cnt)
-        dec, dr = ctx.copy_decisions_np()
-        a = cnt // 2
-        parts = [ctx.run_batch_np(begin, a), ctx.run_batch_np(begin + a, cnt - a)] if a else [ctx.run_batch_np(begin, cnt)]
-        assert np.concatenate([p[1] for p in parts]).tobytes() == pi.tobytes()
-        assert sum(p[0].digest for p in parts) & M64 == s.digest & M64
-        assert sum(p[0].decided_processes for p in parts) == s.decided_processes
-        ids = np.array(sorted({begin + (7 * j) % cnt for j in range(min(cnt, 9))}, reverse=True), np.uint64)
-        fs, fr = ctx.fetch_np(ids)
-        for j, i in enumerate(int(x) - begin for x in ids):
-            assert fs[j].tobytes() == pi[i].tobytes()
-            assert (fr[j]["decision"] == dec[i]).all() and (fr[j]["decision_round"] == dr[i]).all()
-            assert (fr[j]["halt_round"] == 2).all()
+    for rec in sharding_and_fetch(psync.TwoPhaseCommit(), n, cnt):
+        assert (rec["halt_round"] == 2).all()
 
 
 def test_multi_device_context_equals_one_device():
-    """A device-list context ([0, 0]: two per-device contexts on the one card) gives the single
-    context's summary, per-instance summaries, decisions and fetched records."""
-    n, cnt, begin = 130, 201, 77
-    out = []
-    for devices in (None, [0, 0]):
-        with psync.GpuRound(psync.TwoPhaseCommit(coord=129), n, seed=6, batch_capacity=cnt, devices=devices) as g:
-            r = g.run(begin, cnt, per_instance=True)
-            f = g.fetch([begin, begin + 100, begin + cnt - 1])
-            out.append((abi.summary_to_list(r.summary)[:-1],
-                        [(s.digest, tuple(s.first_fail), s.term_round, s.n_decided) for s in r.per_instance],
-                        g.decisions(), [s.digest for s in f[0]],
-                        [(x.decision, x.decision_round, x.halt_round, x.final_x) for x in f[1]]))
-    assert out[0] == out[1]
+    assert_multi_device_equals_one_device(psync.TwoPhaseCommit(coord=129))
 
 
 # ------------------------------------------------------------------------------------ 5. generic Spec
@@ -273,12 +167,12 @@ def test_reference_spec_equals_the_builtin_checks(n, mode):
         g.load_schedule(0, I, ho)
         built = g.run(0, I, per_instance=True)
         sp = g.run_spec(0, I, prog, per_instance=True)
-    rows = lambda pi: [(tuple(s.first_fail)[:4], s.term_round, s.digest) for s in pi]  # noqa: E731
-    assert rows(sp.per_instance) == rows(built.per_instance)
+    built_rows = spec_rows(built.per_instance, 4, digest=True)
+    assert spec_rows(sp.per_instance, 4, digest=True) == built_rows
     assert list(sp.summary.fail_count)[:4] == list(built.summary.fail_count)[:4]
     assert built.summary.fail_count[3] >= I // 4 and built.summary.fail_count[2] == 0
     runs = [py_tpc(n, coord, votes[i], ho_ints(ho[i]), R, mutant=True) for i in range(I)]
-    assert [(tuple(r.first_fail), r.term_round) for r in runs] == [x[:2] for x in rows(built.per_instance)]
+    assert [(tuple(r.first_fail), r.term_round) for r in runs] == [x[:2] for x in built_rows]
 
 
 # ------------------------------------------------------------------------------------ 6. adversary

@@ -19,6 +19,8 @@ import pytest
 
 from round_amd import abi, psync
 
+from restatement import py_champ, py_improve
+
 NEVER = abi.PSG_NEVER
 FULL4 = 0b1111
 
@@ -319,28 +321,8 @@ def test_java_random_first_boolean(oracle_mod):
     assert seen == {True, False}
 
 
-def _py_improve(h):
-    m = 0xFFFFFFFF
-    x = (h + (~(h << 9) & m)) & m
-    x ^= x >> 14
-    x = (x + (x << 4)) & m
-    x ^= x >> 10
-    return x
-
-
-def _py_champ(keys, shift=0):
-    groups = {}
-    for k in keys:
-        groups.setdefault((_py_improve(k) >> shift) & 31, []).append(k)
-    out = [g[0] for f, g in sorted(groups.items()) if len(g) == 1]
-    for f, g in sorted(groups.items()):
-        if len(g) > 1:
-            out += _py_champ(g, shift + 5)
-    return out
-
-
 def test_scala_map_order(oracle_mod):
-    assert oracle_mod.scala_improve(0) == _py_improve(0) == 0xFF83EF00
+    assert oracle_mod.scala_improve(0) == py_improve(0) == 0xFF83EF00
     rng = random.Random(9)
     for m in range(1, 40):
         keys = sorted(rng.sample(range(256), m))
@@ -348,8 +330,8 @@ def test_scala_map_order(oracle_mod):
         if m <= 4:
             assert got == keys  # Map1..Map4: insertion order
         else:
-            assert got == _py_champ(keys)
+            assert got == py_champ(keys)
         assert sorted(got) == keys
         assert oracle_mod.scala_map_order(keys, abi.PSG_TIE_MIN_PID) == keys
     # improve() is a bijection, so distinct pids never collide
-    assert len({_py_improve(h) for h in range(1 << 16)}) == 1 << 16
+    assert len({py_improve(h) for h in range(1 << 16)}) == 1 << 16

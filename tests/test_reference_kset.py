@@ -9,7 +9,7 @@ decider in Map iteration order (insertion order = ascending pid for <= 4 entries
 CHAMP order for >= 5).
 
 This file restates the algorithm independently in pure Python (a dict built exactly like
-`content`, `_py_champ` for the Map order) and checks the C++ oracle against it: two
+`content`, `py_champ` for the Map order) and checks the C++ oracle against it: two
 hand-built known-answer schedules (n = 5 insertion order, n = 8 CHAMP order) where a
 non-decider hears two deciders holding different `t`, and random explicit schedules. The
 GPU tests run the same schedules through `psg_load_schedule` and compare with the oracle.
@@ -18,7 +18,8 @@ import numpy as np
 import pytest
 
 from round_amd import abi, psync
-from test_oracle_kat import _py_champ
+
+from restatement import py_champ
 
 NEVER = abi.PSG_NEVER
 
@@ -27,7 +28,7 @@ def _map_order(keys, tiebreak):
     keys = sorted(keys)  # the HO harness inserts senders in ascending pid
     if tiebreak == abi.PSG_TIE_MIN_PID or len(keys) <= 4:
         return keys
-    return _py_champ(keys)
+    return py_champ(keys)
 
 
 def py_kset(n, k, init, ho, tiebreak=abi.PSG_TIE_CHAMP, adopt="last"):
@@ -106,7 +107,7 @@ def _oracle_recs(oracle_mod, n, k, init, ho, tiebreak):
 
 
 def test_champ_order_of_kat_mailbox():
-    assert _py_champ([1, 3, 5, 6, 7]) == [5, 1, 6, 7, 3]
+    assert py_champ([1, 3, 5, 6, 7]) == [5, 1, 6, 7, 3]
 
 
 @pytest.mark.parametrize("kat,expect_last,expect_first", [

@@ -44,33 +44,9 @@ symbols onto LastVoting.scala's state (LastVoting.scala:80-212):
 import numpy as np
 import pytest
 
-from round_amd import abi, psync
+from round_amd import psync
 
-NF = 9
-X, DECIDED, DECISION, TS, READY, COMMIT, VOTE = 0, 1, 2, 3, 4, 5, 6
-
-
-def _maxts_ok(box, val):
-    """maxTSdef (LvExample.scala:78-97) for one non-empty map box = {pid: (value, ts)}."""
-    return any(box[j][0] == val and all(box[i][0] == val or box[i][1] <= box[j][1] for i in box) for j in box)
-
-
-def _state(row, n):
-    d = {f: [int(v) for v in row[f]] for f in (X, DECIDED, DECISION, TS, READY, COMMIT, VOTE)}
-    return {
-        "data": [d[DECISION][i] if d[DECIDED][i] else d[X][i] for i in range(n)],
-        "decided": [bool(v) for v in d[DECIDED]],
-        "ts": d[TS], "ready": [bool(v) for v in d[READY]], "commit": [bool(v) for v in d[COMMIT]],
-        "vote": d[VOTE],
-    }
-
-
-def _frame(pre, post, names, n):
-    for f in names:
-        for i in range(n):
-            if pre[f][i] != post[f][i]:
-                return f"frame {f} of p{i}: {pre[f][i]} -> {post[f][i]}"
-    return None
+from restatement import LV_MODEL_CASES, NF, lv_agreement, lv_frame, lv_invariant1, lv_maxts_ok, lv_state
 
 
 def _round1(n, r, k, pre, post, ho):
@@ -83,11 +59,11 @@ def _round1(n, r, k, pre, post, ho):
         r0 = i == co and k == 0 and len(mb) > 0 and not majority
         if majority or r0:
             used_r0 |= r0
-            if not (post["commit"][i] and _maxts_ok(mb, post["vote"][i])):
+            if not (post["commit"][i] and lv_maxts_ok(mb, post["vote"][i])):
                 return f"coordinator p{i}: vote1 {post['vote'][i]} / commit1 {post['commit'][i]} vs maxTS", used_r0
         elif post["commit"][i]:
             return f"p{i}: commit1 without a majority at the coordinator", used_r0
-    return _frame(pre, post, ("decided", "data", "ready", "ts"), n), used_r0
+    return lv_frame(pre, post, ("decided", "data", "ready", "ts"), n), used_r0
 
 
 def _round2(n, r, pre, post, ho):
@@ -99,7 +75,7 @@ def _round2(n, r, pre, post, ho):
                 return f"p{i}: data1/ts1 {post['data'][i]}/{post['ts'][i]} != vote {pre['vote'][co]}/{r}"
         elif post["data"][i] != pre["data"][i] or post["ts"][i] != pre["ts"][i]:
             return f"p{i}: data/ts changed without the coordinator's vote"
-    return _frame(pre, post, ("decided", "ready", "commit", "vote"), n)
+    return lv_frame(pre, post, ("decided", "ready", "commit", "vote"), n)
 
 
 def _round3(n, r, pre, post, ho):
@@ -109,7 +85,7 @@ def _round3(n, r, pre, post, ho):
         mb = [j for j in range(n) if i == co and pre["ts"][j] == r and j in ho[i]]
         if post["ready"][i] != (i == co and n < 2 * len(mb)):
             return f"p{i}: ready1 {post['ready'][i]} with |mailbox3| {len(mb)}"
-    return _frame(pre, post, ("decided", "data", "commit", "vote", "ts"), n)
+    return lv_frame(pre, post, ("decided", "data", "commit", "vote", "ts"), n)
 
 
 def _round4(n, r, pre, post, ho):
@@ -123,56 +99,11 @@ def _round4(n, r, pre, post, ho):
             return f"p{i}: data/decided changed without the coordinator's vote"
         if post["commit"][i] or post["ready"][i]:
             return f"p{i}: commit1/ready1 not reset"
-    return _frame(pre, post, ("vote", "ts"), n)
+    return lv_frame(pre, post, ("vote", "ts"), n)
 
 
-def _invariant1(n, r, s, data0):
-    """LvExample.scala:221-238, V and the phase type finitized exactly: v ranges over the
-    data values (A is a non-empty majority), t over the timestamps (A = {i : t <= ts(i)}
-    only changes at a timestamp, and every ts <= r)."""
-    co = r % n
-    no_dec = all(not s["decided"][i] and not s["ready"][i] for i in range(n))
-    maj = False
-    if not no_dec:
-        for t in sorted(set(s["ts"])):
-            if t > r:
-                continue
-            A = [i for i in range(n) if t <= s["ts"][i]]
-            if not n < 2 * len(A):
-                continue
-            for v in set(s["data"][i] for i in A):
-                if all((i not in A or s["data"][i] == v) and (not s["decided"][i] or s["data"][i] == v) and
-                       (not s["commit"][i] or s["vote"][i] == v) and (not s["ready"][i] or s["vote"][i] == v) and
-                       (s["ts"][i] != r or s["commit"][co]) for i in range(n)):
-                    maj = True
-                    break
-            if maj:
-                break
-    valid = all(s["data"][i] in data0 for i in range(n))
-    return (no_dec or maj) and valid
-
-
-def _agreement(n, s):
-    """LvExample.scala:60."""
-    return len({s["data"][i] for i in range(n) if s["decided"][i]}) <= 1
-
-
-# (n, count, schedule, tiebreak, value_range)
-H = psync.HOSchedule
-CASES = [
-    (4, 300, H(drop_log2=2, good_round=0.0), abi.PSG_TIE_CHAMP, 3),
-    (5, 300, H(drop_log2=1, good_round=0.0, crash_fmax=2), abi.PSG_TIE_CHAMP, 4),
-    (7, 300, H(drop_log2=2, good_round=0.0, self_bit=False), abi.PSG_TIE_CHAMP, 3),
-    (16, 200, H(drop_log2=3, good_round=0.0, crash_fmax=7), abi.PSG_TIE_CHAMP, 5),
-    (16, 200, H(drop_log2=1, good_round=0.0), abi.PSG_TIE_MIN_PID, 5),
-    (64, 60, H(drop_log2=4, good_round=0.0, crash_fmax=31), abi.PSG_TIE_CHAMP, 32767),
-    (64, 60, H(drop_log2=2, good_round=0.0), abi.PSG_TIE_CHAMP, 3),
-    (64, 60, H(drop_log2=2, good_round=0.0, crash_fmax=20), abi.PSG_TIE_MIN_PID, 6),
-]
-
-
-@pytest.mark.parametrize("n,count,sched,tb,V", CASES,
-                         ids=[f"n{c[0]}-{i}" for i, c in enumerate(CASES)])
+@pytest.mark.parametrize("n,count,sched,tb,V", LV_MODEL_CASES,
+                         ids=[f"n{c[0]}-{i}" for i, c in enumerate(LV_MODEL_CASES)])
 def test_oracle_rounds_satisfy_lv_model(n, count, sched, tb, V, oracle_mod):
     R = 24
     cfg = psync.make_config(psync.LastVoting(), n, R, seed=900 + n, value_range=V, schedule=sched, tiebreak=tb)
@@ -181,9 +112,9 @@ def test_oracle_rounds_satisfy_lv_model(n, count, sched, tb, V, oracle_mod):
     W = (n + 63) // 64
     stats = {"rounds": 0, "r0_shortcut": 0, "decisions": 0, "commits": 0}
     for inst in range(count):
-        states = [_state(tr[inst, c], n) for c in range(R + 1)]
+        states = [lv_state(tr[inst, c], n) for c in range(R + 1)]
         data0 = set(states[0]["data"])
-        assert _invariant1(n, 0, states[0], data0)
+        assert lv_invariant1(n, 0, states[0], data0)
         for k in range(R):
             pre, post, r = states[k], states[k + 1], k // 4
             halted = [pre["decided"][i] for i in range(n)]  # LV decides and exits in the same round
@@ -208,8 +139,8 @@ def test_oracle_rounds_satisfy_lv_model(n, count, sched, tb, V, oracle_mod):
             assert all(not pre["decided"][i] or (post["decided"][i] and pre["data"][i] == post["data"][i])
                        for i in range(n)), (inst, k)
             rr = (k + 1) // 4  # the phase of the post-state (round4 moves r to r + 1)
-            assert _invariant1(n, rr, post, data0), f"instance {inst}: invariant1 false after round {k}"
-            assert _agreement(n, post), (inst, k)
+            assert lv_invariant1(n, rr, post, data0), f"instance {inst}: invariant1 false after round {k}"
+            assert lv_agreement(n, post), (inst, k)
             stats["rounds"] += 1
             stats["commits"] += sum(post["commit"]) if k % 4 == 0 else 0
         stats["decisions"] += sum(states[R]["decided"])
@@ -227,7 +158,7 @@ def test_mutant_breaks_the_model(oracle_mod):
     broken = 0
     for inst in range(count):
         for k in range(2, R, 4):
-            pre, post = _state(tr[inst, k], n), _state(tr[inst, k + 1], n)
+            pre, post = lv_state(tr[inst, k], n), lv_state(tr[inst, k + 1], n)
             halted = pre["decided"]
             sets = [set() if halted[p] else {q for q in range(n) if (int(ho[inst, k, p, 0]) >> q) & 1 and not halted[q]}
                     for p in range(n)]

@@ -23,11 +23,10 @@ import numpy as np
 import pytest
 
 from round_amd import abi, psync
-import test_reference_lv as LVX
-from test_reference_tr import _mmor
 
-NF = 9
-X, DECIDED = 0, 1
+from restatement import (DECIDED, LV_MODEL_CASES, NF, X, lv_agreement, lv_frame, lv_invariant1, lv_maxts_ok, lv_state,
+                         mmor)
+
 H = psync.HOSchedule
 
 
@@ -116,7 +115,7 @@ def test_gpu_otr2_adoptions_satisfy_ensuring():
                 if len(mb) > 2 * n // 3:
                     v1 = int(xs[k + 1][i, p])
                     assert ensuring(mb, v1), (i, k, p, mb, v1)
-                    assert v1 == _mmor(mb)  # and OtrExample.scala:67-75's defs
+                    assert v1 == mmor(mb)  # and OtrExample.scala:67-75's defs
                     checked += 1
     assert checked > 1000
 
@@ -132,7 +131,7 @@ def _otr_nm(n):
         """OtrExampleNoMailbox.scala:81-98 (mmor by defs 70-79)."""
         for i in range(n):
             if len(ho[i]) > tt:
-                m = _mmor([data[j] for j in ho[i]])
+                m = mmor([data[j] for j in ho[i]])
                 want = True if len(value_is(ho[i], data, m)) > tt else decided[i]
                 if data1[i] != m or decided1[i] != want:
                     return f"p{i}"
@@ -258,11 +257,11 @@ def _lv_rounds_nm(n, k, pre, post, ho):
         for i in range(n):
             if i == co and (maj(ho[i]) or (k == 0 and ho[i])):
                 box = {j: (pre["data"][j], pre["ts"][j]) for j in ho[i]}
-                if not (post["commit"][i] and LVX._maxts_ok(box, post["vote"][i])):
+                if not (post["commit"][i] and lv_maxts_ok(box, post["vote"][i])):
                     return f"round1: coordinator p{i}"
             elif post["commit"][i]:
                 return f"round1: p{i} commit1"
-        return LVX._frame(pre, post, ("decided", "data", "ready", "ts"), n)
+        return lv_frame(pre, post, ("decided", "data", "ready", "ts"), n)
     if slot == 1:  # round2
         for i in range(n):
             if co in ho[i]:
@@ -270,12 +269,12 @@ def _lv_rounds_nm(n, k, pre, post, ho):
                     return f"round2: p{i}"
             elif post["data"][i] != pre["data"][i] or post["ts"][i] != pre["ts"][i]:
                 return f"round2: p{i} frame"
-        return LVX._frame(pre, post, ("decided", "ready", "commit", "vote"), n)
+        return lv_frame(pre, post, ("decided", "ready", "commit", "vote"), n)
     if slot == 2:  # round3
         for i in range(n):
             if post["ready"][i] != (i == co and maj(ho[i])):
                 return f"round3: p{i} ready1"
-        return LVX._frame(pre, post, ("decided", "data", "commit", "vote", "ts"), n)
+        return lv_frame(pre, post, ("decided", "data", "commit", "vote", "ts"), n)
     for i in range(n):  # round4
         if co in ho[i]:
             if post["data"][i] != pre["vote"][co] or not post["decided"][i]:
@@ -284,7 +283,7 @@ def _lv_rounds_nm(n, k, pre, post, ho):
             return f"round4: p{i} frame"
         if post["commit"][i] or post["ready"][i]:
             return f"round4: p{i} reset"
-    return LVX._frame(pre, post, ("vote", "ts"), n)
+    return lv_frame(pre, post, ("vote", "ts"), n)
 
 
 def _invariant1c(n, r, s, data0):
@@ -324,7 +323,7 @@ def _lv_transitions(oracle_mod, alg, n, count, sched, tb, V, R=24, seed=700):
     ho, _ = oracle_mod.materialize_schedule(cfg, 0, count)
     W = (n + 63) // 64
     for inst in range(count):
-        states = [LVX._state(tr[inst, c], n) for c in range(R + 1)]
+        states = [lv_state(tr[inst, c], n) for c in range(R + 1)]
         for k in range(R):
             pre = states[k]
             sets = []
@@ -337,24 +336,24 @@ def _lv_transitions(oracle_mod, alg, n, count, sched, tb, V, R=24, seed=700):
             yield inst, k, states, sets
 
 
-@pytest.mark.parametrize("n,count,sched,tb,V", LVX.CASES, ids=[f"n{c[0]}-{i}" for i, c in enumerate(LVX.CASES)])
+@pytest.mark.parametrize("n,count,sched,tb,V", LV_MODEL_CASES, ids=[f"n{c[0]}-{i}" for i, c in enumerate(LV_MODEL_CASES)])
 def test_oracle_rounds_satisfy_lv_nomailbox_model(oracle_mod, n, count, sched, tb, V):
     used = {"maxts": 0, "rounds": 0}
     for inst, k, states, sets in _lv_transitions(oracle_mod, psync.LastVoting(), n, count, sched, tb, V):
         pre, post = states[k], states[k + 1]
         data0 = set(states[0]["data"])
         if k == 0:  # initial state implies invariant; validity holds initially
-            assert LVX._invariant1(n, 0, pre, data0) and _invariant1c(n, 0, pre, data0)
+            assert lv_invariant1(n, 0, pre, data0) and _invariant1c(n, 0, pre, data0)
         ho = _heard(n, k, pre, sets)
         err = _lv_rounds_nm(n, k, pre, post, ho)
         assert err is None, f"instance {inst} round {k}: {err}"
         rr = (k + 1) // 4
         # invariant 1 is inductive at round 1 .. 4 (the ignored VCs), and 1c (1d = 1 with the
         # comprehension variable renamed); invariant implies agreement
-        if LVX._invariant1(n, k // 4, pre, data0):
-            assert LVX._invariant1(n, rr, post, data0), f"instance {inst}: invariant1 not inductive at {k}"
+        if lv_invariant1(n, k // 4, pre, data0):
+            assert lv_invariant1(n, rr, post, data0), f"instance {inst}: invariant1 not inductive at {k}"
         assert _invariant1c(n, rr, post, data0)
-        assert LVX._agreement(n, post)
+        assert lv_agreement(n, post)
         if k % 4 == 0:
             co = (k // 4) % n
             used["maxts"] += _maxts_lemma(n, pre, post, co, ho[co])

@@ -1,9 +1,9 @@
 """TwoPhaseCommit pinned to the reference: a literal restatement, the formal model, the Spec.
 
-`py_tpc` restates `TpcProcess` (example/TwoPhaseCommit.scala:15-79) in pure Python under explicit
-HO sets, with send / mailbox / update per round as the source writes them, and evaluates the Spec
-(:93-105) on the state variable `decision` after every round. It is the reference side of the GPU
-tests (tests/test_gpu_tpc.py): the oracle library has no TwoPhaseCommit.
+`py_tpc` (tests/restatement.py) restates `TpcProcess` (example/TwoPhaseCommit.scala:15-79) in pure
+Python under explicit HO sets, with send / mailbox / update per round as the source writes them, and
+evaluates the Spec (:93-105) on the state variable `decision` after every round. It is the reference
+side of the GPU tests (tests/test_gpu_tpc.py): the oracle library has no TwoPhaseCommit.
 
 The reference also holds a formal model of the algorithm, psync/logic/TpcExample.scala. Its
 transition relations `round1a` (:45-60) and `round2a` (:90-101) and its `invariant1`, `agreement`
@@ -27,168 +27,14 @@ import pytest
 from round_amd import abi, formula as F, lib, psync, schedules as S
 
 import formula_ref
+from restatement import NEVER, NONE32, TPC_KAT_IDS, TPC_KATS, full_ho, ho_ints, py_tpc
+from restatement import tpc_kat_full, tpc_kat_mutant_n5 as kat_mutant_n5, tpc_kat_two_rounds as kat_two_rounds
 
-NEVER = abi.PSG_NEVER
-NONE32 = -(1 << 31)
 TPC = abi.PSG_ALG_TPC
 
 
-class TpcRun:
-    """Result of py_tpc: per-process records, the Spec's verdicts, the states of every check point."""
-
-    def __init__(self, n, R):
-        self.n, self.R = n, R
-        self.rec = []         # per p: (decision, decision_round, halt_round, vote) as the C ABI reports them
-        self.states = []      # per check point: list of decision (None / False / True) per p
-        self.first_fail = [NEVER] * 4   # Safety, Invariant0, UniformAgreement, Validity
-        self.term_round = NEVER
-        self.n_decided = 0
-
-
-def py_tpc(n, coord, votes, ho, R, mutant=False):
-    """TpcProcess under explicit HO sets ho[k][p] (bit q: p hears q in round k), R rounds.
-    mutant: the coordinator drops `mailbox.size == n` (:51)."""
-    vote = [bool(v) for v in votes]          # init(io), :22-27: vote = io.canCommit
-    decision = [None] * n                    # decision = None
-    halted = [False] * n
-    cb = [None] * n                          # (value passed to callback.decide, round), :73
-    out = TpcRun(n, R)
-
-    def check(c):
-        defined = [d for d in decision if d is not None]
-        validity = (not any(d is True for d in decision)) or all(vote)            # :104
-        agreement = all(a == b for a in defined for b in defined)                 # :102
-        inv = validity and agreement                                              # :94-95
-        for s, ok in enumerate((inv, inv, agreement, validity)):
-            if not ok and out.first_fail[s] == NEVER:
-                out.first_fail[s] = c
-        if out.term_round == NEVER and len(defined) == n:
-            out.term_round = c
-        out.states.append(list(decision))
-
-    check(0)
-    for k in range(R):
-        slot = k % 3
-        senders = [q for q in range(n) if not halted[q]]
-        # send(): Map[destination -> payload] of every non-halted process
-        sent = {}
-        for q in senders:
-            if slot == 0:
-                sent[q] = {p: True for p in range(n)} if q == coord else {}       # :31-34 broadcast(true)
-            elif slot == 1:
-                sent[q] = {coord: vote[q]}                                        # :43-45
-            else:
-                if q == coord:
-                    assert decision[q] is not None  # decision.get (:63): slot 1 of this phase ran first
-                    sent[q] = {p: decision[q] for p in range(n)}
-                else:
-                    sent[q] = {}
-        inbox = [{} for _ in range(n)]  # what was sent to p (sender -> payload), before the HO filter
-        for q in senders:
-            for p, v in sent[q].items():
-                inbox[p][q] = v
-        new = list(decision)
-        exits = []
-        for p in senders:
-            mailbox = {q: v for q, v in inbox[p].items() if (ho[k][p] >> q) & 1}
-            if slot == 1:
-                if p == coord:                                                    # :50-56
-                    if (mutant or len(mailbox) == n) and all(mailbox.values()):
-                        new[p] = True
-                    else:
-                        new[p] = False
-            elif slot == 2:
-                if len(mailbox) > 0:                                              # :70-72
-                    new[p] = next(iter(mailbox.values()))                         # mailbox.head._2
-                cb[p] = (new[p], k)                                               # callback.decide(decision)
-                exits.append(p)                                                   # exitAtEndOfRound()
-        decision = new
-        for p in exits:
-            halted[p] = True
-        check(k + 1)
-    for p in range(n):
-        if cb[p] is None:
-            out.rec.append((NONE32, -1, -1, int(vote[p])))
-        elif cb[p][0] is None:                       # decide(None): coordinator suspected, not a decision
-            out.rec.append((NONE32, -1, cb[p][1], int(vote[p])))
-        else:
-            out.rec.append((int(cb[p][0]), cb[p][1], cb[p][1], int(vote[p])))
-    out.n_decided = sum(1 for r in out.rec if r[1] >= 0)
-    return out
-
-
-def ho_ints(ho_arr):
-    """uint64 [R][n][W] -> Python ints [R][n]."""
-    R, n, W = ho_arr.shape
-    return [[sum(int(ho_arr[k, p, w]) << (64 * w) for w in range(W)) for p in range(n)] for k in range(R)]
-
-
-def full_ho(n, R):
-    return [[(1 << n) - 1] * n for _ in range(R)]
-
-
 # ------------------------------------------------------------------------------------ 1. hand KATs
-def kat_full():
-    return 3, 0, (1, 1, 1), full_ho(3, 3), 3
-
-
-def kat_coord_misses_vote():
-    ho = full_ho(3, 3)
-    ho[1][0] = 0b011  # the coordinator does not hear p2's vote
-    return 3, 0, (1, 1, 1), ho, 3
-
-
-def kat_receiver_misses_coord():
-    ho = full_ho(3, 3)
-    ho[2][1] = 0b110  # p1 does not hear the coordinator's decision
-    return 3, 0, (1, 1, 1), ho, 3
-
-
-def kat_coord_deaf_to_itself_slot1():
-    ho = full_ho(3, 3)
-    ho[1][0] = 0b110  # pure HO: the coordinator's own vote is not delivered
-    return 3, 0, (1, 1, 1), ho, 3
-
-
-def kat_coord_deaf_to_itself_slot2():
-    ho = full_ho(3, 3)
-    ho[2][0] = 0b110  # pure HO: the coordinator does not hear its own broadcast
-    return 3, 0, (1, 1, 1), ho, 3
-
-
-def kat_two_rounds():
-    return 3, 0, (1, 1, 1), full_ho(3, 2), 2
-
-
-def kat_mutant_n5():
-    """n = 5, coord = 0, p3 votes no and its slot-1 link to the coordinator is dropped."""
-    ho = full_ho(5, 3)
-    ho[1][0] = 0b10111
-    return 5, 0, (1, 1, 1, 0, 1), ho, 3
-
-
-def kat_coord_crashed_from_round2():
-    """The coordinator crashes by send omission from round 2: nobody else hears its decision."""
-    n = 5
-    ho = full_ho(n, 3)
-    for p in range(1, n):
-        ho[2][p] = ((1 << n) - 1) & ~1
-    return n, 0, (1, 1, 1, 1, 1), ho, 3
-
-
-# (kat, per-process (decision, decision_round, halt_round), first_fail, term_round, n_decided)
-KATS = [
-    (kat_full, [(1, 2, 2)] * 3, [NEVER] * 4, 3, 3),
-    (kat_coord_misses_vote, [(0, 2, 2)] * 3, [NEVER] * 4, 3, 3),
-    (kat_receiver_misses_coord, [(1, 2, 2), (NONE32, -1, 2), (1, 2, 2)], [NEVER] * 4, NEVER, 2),
-    (kat_coord_deaf_to_itself_slot1, [(0, 2, 2)] * 3, [NEVER] * 4, 3, 3),
-    (kat_coord_deaf_to_itself_slot2, [(1, 2, 2)] * 3, [NEVER] * 4, 3, 3),
-    (kat_two_rounds, [(NONE32, -1, -1)] * 3, [NEVER] * 4, NEVER, 0),
-    (kat_coord_crashed_from_round2, [(1, 2, 2)] + [(NONE32, -1, 2)] * 4, [NEVER] * 4, NEVER, 1),
-]
-
-
-@pytest.mark.parametrize("kat,recs,ff,term,nd", KATS, ids=[k[0].__name__ for k in KATS])
+@pytest.mark.parametrize("kat,recs,ff,term,nd", TPC_KATS, ids=TPC_KAT_IDS)
 def test_hand_kats(kat, recs, ff, term, nd):
     n, coord, votes, ho, R = kat()
     run = py_tpc(n, coord, votes, ho, R)
@@ -352,7 +198,7 @@ def test_reference_spec_equals_the_restatements_checks(oracle_mod):
 def test_abi_row():
     L = lib.load()
     assert L.psg_alg_from_class(b"example.TwoPhaseCommit") == 10 == TPC
-    assert L.psg_check_count(TPC) == 4
+    assert L.psg_check_count(TPC) == 4 == len(py_tpc(*tpc_kat_full()).first_fail)
     assert lib.check_names(TPC) == ["Safety", "Invariant0", "UniformAgreement", "Validity"]
     assert L.psg_check_name(TPC, 4) is None
     assert psync.ALGORITHMS["example.TwoPhaseCommit"]().violation_slots == [0, 2, 3]

@@ -26,24 +26,7 @@ import pytest
 
 from round_amd import psync
 
-NF = 9  # trace fields (include/psg.h enum psg_field)
-X, DECIDED = 0, 1
-
-
-def _mmor(mailbox_vals):
-    """OtrExample.scala:67-75 defs, literally: the value with card >= 1 whose card is
-    maximal and which is Leq every other value of maximal card."""
-    best = None
-    for v in set(mailbox_vals):
-        c = mailbox_vals.count(v)
-        if c < 1:
-            continue
-        ok = all(mailbox_vals.count(p) <= c for p in set(mailbox_vals))
-        ok = ok and all(v <= p for p in set(mailbox_vals) if mailbox_vals.count(p) == c)
-        if ok:
-            assert best is None, "defs determine mmor uniquely"
-            best = v
-    return best
+from restatement import DECIDED, NF, X, mmor
 
 
 def _tr(n, data, decided, ho, data1, decided1):
@@ -52,7 +35,7 @@ def _tr(n, data, decided, ho, data1, decided1):
     for i in range(n):
         mailbox = {j: data[j] for j in ho[i]}              # KeySet == ho(i), LookUp == data(j)
         if len(mailbox) > two_third:                        # twoThirdMap(mailbox(i))
-            m = _mmor(list(mailbox.values()))
+            m = mmor(list(mailbox.values()))
             if data1[i] != m:
                 return f"p{i}: data1 {data1[i]} != mmor {m}"
             a = [j for j in mailbox if mailbox[j] == m]     # valueIs(mmor(i))

@@ -18,13 +18,12 @@ import pytest
 from round_amd import abi, formula as F, lib, psync
 
 import spec_cases
-import test_spec_text as TT
 
 CASES = [(f"ref-{a}", a, 64, lambda a=a: F.to_text(F.REFERENCE_SPECS[a]())) for a in sorted(F.REFERENCE_SPECS)]
 CASES += [(c[0], c[1].alg_id, c[2], lambda mk=c[4]: F.to_text(mk())) for c in spec_cases.CUSTOM]
-CASES += [("let", abi.PSG_ALG_LAST_VOTING, 8, lambda: TT.LV_MAJORITY_LET),
-          ("flat-binders", abi.PSG_ALG_OTR, 8, lambda: TT.AGREEMENT_FLAT),
-          ("nary-and", abi.PSG_ALG_BENOR, 8, lambda: TT.NARY_AND)]
+CASES += [("let", abi.PSG_ALG_LAST_VOTING, 8, lambda: spec_cases.LV_MAJORITY_LET),
+          ("flat-binders", abi.PSG_ALG_OTR, 8, lambda: spec_cases.AGREEMENT_FLAT),
+          ("nary-and", abi.PSG_ALG_BENOR, 8, lambda: spec_cases.NARY_AND)]
 
 
 @pytest.mark.parametrize("cid,alg,n,text", CASES, ids=[c[0] for c in CASES])
@@ -164,7 +163,7 @@ def test_hiprtc_compile_on_the_host(tmp_path):
     assert prog.module_path.startswith(str(tmp_path)) and os.path.getsize(prog.module_path) > 10_000
     with open(prog.module_path, "rb") as f:
         assert f.read(4) == b"\x7fELF"
-    TT._same(prog, lib.spec_from_text(text, abi.PSG_ALG_OTR))
+    spec_cases.same_program(prog, lib.spec_from_text(text, abi.PSG_ALG_OTR))
     mtime = os.path.getmtime(prog.module_path)
     again = lib.spec_compile_native(text, abi.PSG_ALG_OTR, True, 64, cache_dir=str(tmp_path))
     assert again.module_path == prog.module_path and os.path.getmtime(again.module_path) == mtime

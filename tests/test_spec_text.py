@@ -15,13 +15,9 @@ import pytest
 from round_amd import abi, formula as F, lib, psync
 
 import spec_cases
+from spec_cases import AGREEMENT_FLAT, LV_MAJORITY_LET, NARY_AND, same_program
 
 P, V, n, r, init = F.P, F.V, F.n, F.r, F.init
-
-
-def _same(a, b):
-    assert (a.code, a.slot_entry, a.slot_flags, a.term_entry, a.n_vars, a.slot_names) == \
-           (b.code, b.slot_entry, b.slot_flags, b.term_entry, b.n_vars, b.slot_names)
 
 
 @pytest.mark.parametrize("alg", sorted(F.REFERENCE_SPECS))
@@ -30,49 +26,23 @@ def test_reference_specs_compile_identically(alg):
     text = F.to_text(spec)
     want = F.compile_spec(spec, alg)
     got = lib.spec_from_text(text, alg)
-    _same(got, want)
+    same_program(got, want)
     assert got.alg == alg
-    _same(F.compile_spec(F.from_text(text), alg), want)
+    same_program(F.compile_spec(F.from_text(text), alg), want)
 
 
 @pytest.mark.parametrize("cid,alg,nn,kw,mk", spec_cases.CUSTOM, ids=[c[0] for c in spec_cases.CUSTOM])
 def test_custom_specs_compile_identically(cid, alg, nn, kw, mk):
     spec = mk()
-    _same(lib.spec_from_text(F.to_text(spec), alg.alg_id), F.compile_spec(spec, alg.alg_id))
+    same_program(lib.spec_from_text(F.to_text(spec), alg.alg_id), F.compile_spec(spec, alg.alg_id))
 
 
 # hand-written texts in FormulaExtractor's shapes, each with its DSL equivalent
-LV_MAJORITY_LET = """
-(Spec (phase 1)
-  (invariants
-    (Exists ((v Int) (t Int))
-      (Exists ((A Set))
-        (App And (App Eq (Var A) (Comprehension ((i pid)) (App Geq (App ts (Var i)) (Var t))))
-                 (App Gt (App Cardinality (Var A)) (App Divides (Var n) (Lit 2)))
-                 (App Gt (Var r) (Lit 0))
-                 (App Leq (Var t) (App Divides (Var r) (Lit 4)))
-                 (ForAll ((i pid)) (App Implies (App In (Var i) (Var A)) (App Eq (App x (Var i)) (Var v)))))))))
-"""
-
-
 def _lv_majority_dsl():
     def body(v, t):
         A = P.filter(lambda i: i.ts >= t)
         return (A.size > n // 2) & (r > 0) & (t <= r // 4) & P.forall(lambda i: A.contains(i).implies(i.x == v))
     return F.Spec([V.exists(lambda v: V.exists(lambda t: body(v, t)))])
-
-
-AGREEMENT_FLAT = """
-(Spec (phase 1) (invariants)
-  (properties
-    (prop "Agreement" (ForAll ((i pid) (j pid))
-        (App Implies (App And (App decided (Var i)) (App decided (Var j)))
-                     (App Eq (App decision (Var i)) (App decision (Var j))))))
-    (prop "Irrevocability" (ForAll ((i pid))
-        (App Implies (App __old__decided (Var i))
-                     (App And (App decided (Var i)) (App Eq (App __old__decision (Var i)) (App decision (Var i)))))))
-    (prop "Termination" (ForAll ((i pid)) (App decided (Var i))))))
-"""
 
 
 def _agreement_dsl():
@@ -83,14 +53,6 @@ def _agreement_dsl():
             i.decided & (F.old(i.decision) == i.decision)))),
         ("Termination", P.forall(lambda i: i.decided)),
     ])
-
-
-NARY_AND = """
-(Spec (phase 1)
-  (invariants (ForAll ((i pid)) (App And (App Not (App decided (Var i))) (App Geq (App x (Var i)) (Lit 1))
-                                         (App Leq (App x (Var i)) (Lit 100000)) (Lit true))))
-  (safetyPredicate (ForAll ((p pid)) (App Gt (App Cardinality (App HO (Var p))) (App Divides (Var n) (Lit 2))))))
-"""
 
 
 def _nary_dsl():
@@ -105,8 +67,8 @@ def _nary_dsl():
 ], ids=["let", "flat-binders", "nary-and"])
 def test_extractor_shapes(text, mk, alg):
     want = F.compile_spec(mk(), alg)
-    _same(lib.spec_from_text(text, alg), want)
-    _same(F.compile_spec(F.from_text(text), alg), want)
+    same_program(lib.spec_from_text(text, alg), want)
+    same_program(F.compile_spec(F.from_text(text), alg), want)
 
 
 @pytest.mark.parametrize("text,msg", [
