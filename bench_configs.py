@@ -8,6 +8,8 @@
   W2  second-wave algorithms: OTR2, ShortLastVoting, KSetEarlyStopping, EpsilonConsensus
   W3  TwoPhaseCommit n=64, 1e7 instances, 3 rounds (one phase)
   W4  LatticeAgreement n=64, 1e7 instances, 8 rounds, sets over 16 elements
+  S1  OTR at the deployed replica counts n = 4, 8, 16, 32, 1e7 instances, 20 rounds: one instance per
+      wave, and packed (pack=True: 16, 8, 4, 2 instances per wave)
 
 One process per GPU (torchrun), weak scaling, RCCL all-reduce of the summaries.
 Prints one JSON line per configuration (rank 0). Algorithmic bytes per
@@ -58,6 +60,11 @@ def configs(scale):
     # lattice agreement: LatticeAgreement at its defaults (R = 8, U = 16, a quarter of the links lost);
     # (proposed 4 B + decision 4 B) x 2 + init 4
     out.append(("W4_lattice_n64", psync.LatticeAgreement(), 64, int(10_000_000 * s), {}, 20))
+    # small n: one instance per wave against the packed kernel (psg_config.pack, G = 64 / P per wave)
+    for n in (4, 8, 16, 32):
+        out.append((f"S1_otr_n{n}", psync.OTR(), n, int(10_000_000 * s), {}, 24))
+    for n in (4, 8, 16, 32):
+        out.append((f"S1_otr_n{n}_packed", psync.OTR(), n, int(10_000_000 * s), dict(pack=True), 24))
     # generic Spec programs: the reference Specs compiled from the Formula
     # DSL and interpreted on the device over the traced states (psg_run_batch_spec)
     from round_amd import formula
@@ -123,9 +130,9 @@ def main(argv=None):
     results = []
     for row in configs(args.scale):
         name, alg, n, I, kw, balg = row[:6]
-        spec = row[6]() if len(row) > 6 else None
         if args.only and not any(name.startswith(p) for p in args.only.split(",")):
             continue
+        spec = row[6]() if len(row) > 6 else None
         g = psync.GpuRound(alg, n, seed=7, device=dev, batch_capacity=I, **kw)
         begin, _ = rdist.shard(rank, world, I)
         g.load_inputs(begin, I)

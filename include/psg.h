@@ -130,7 +130,11 @@ typedef struct psg_config {
   uint64_t batch_capacity; /* max instances per psg_run_batch call (device buffers sized for it) */
   psg_schedule sched;
   int32_t param2;       /* KSetEarlyStopping k (KSetEarlyStopping.scala:9; param = t) */
-  int32_t reserved;
+  int32_t pack;         /* 0: one instance per wave64 (the default). 1: run psg_run_batch's seeded built-in-check
+                           launch with a packed kernel where the library has one (psg_pack_width > 1): several
+                           instances share a wave, each on P adjacent lanes. Opt-in and bit-exact: the results
+                           are those of pack = 0; every other call of the context runs the same kernels as
+                           with pack = 0. Any other value: PSG_EINVAL */
   double real_param;    /* EpsilonConsensus epsilon (Epsilon.scala:16; param = f) */
   int32_t n_devices;    /* 0: the single device `device`; 1..PSG_MAX_DEVICES: run on devices[0..n_devices)
                            (an ordinal may repeat; batch_capacity is the whole context's, split evenly) */
@@ -276,6 +280,13 @@ const char* psg_check_name(int32_t alg, int32_t slot);
 
 /* Map a reference class name ("example.OTR", "example.LastVoting", ...) to an alg id. */
 int psg_alg_from_class(const char* class_name);
+
+/* Instances per wave64 that a pack = 1 context of algorithm alg at n processes uses for
+ * psg_run_batch without an explicit schedule: G = 64 / P, P the power of two >= n (at least 4).
+ * example.OTR: 16 (n <= 4), 8 (n <= 8), 4 (n <= 16), 2 (n <= 32), 1 above; every other algorithm 1
+ * (no packed kernel yet: pack = 1 changes nothing). PSG_EINVAL for an unknown algorithm or n
+ * outside 1..PSG_MAX_N. A pure host function: no device needed. */
+int psg_pack_width(int32_t alg, int32_t n);
 
 int psg_create(psg_ctx** out, const psg_config* cfg);
 

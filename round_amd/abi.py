@@ -114,7 +114,7 @@ class Config(C.Structure):
         ("batch_capacity", C.c_uint64),
         ("sched", Schedule),
         ("param2", C.c_int32),
-        ("reserved", C.c_int32),
+        ("pack", C.c_int32),  # 1: packed small-n kernels where the library has one
         ("real_param", C.c_double),
         ("n_devices", C.c_int32),
         ("devices", C.c_int32 * PSG_MAX_DEVICES),

@@ -420,8 +420,11 @@ static void summary_add(psg_summary& acc, const psg_summary& p) {
 // One launch of the round kernel over `count` instances and its readback: zero the counters, launch
 // (timed: between the context's events), copy the counters back, synchronise, fill *out (if given).
 // The kernel is the algorithm's own (k_algs), or a fused Spec module's `fused` of at most fused_grid blocks.
+// packable: the launch may go to a packed kernel (psg_run_batch's seeded built-in-check launch).
 static int run_kernel(psg_ctx* c, KArgs& a, uint64_t count, psg_summary* out, bool timed, hipFunction_t fused = nullptr,
-                      uint64_t fused_grid = 0) {
+                      uint64_t fused_grid = 0, bool packable = false) {
+  // several instances per wave: cfg.pack, a packed kernel for (alg, n), no explicit schedule
+  const int pack_g = packable && !fused && c->cfg.pack == 1 && !a.ho_in ? psg_pack_width(c->cfg.alg, c->cfg.n) : 1;
   const int G = groups_per_block(c->W);
   const uint64_t want = (count + G - 1) / G;
   const int grid = (int)std::max<uint64_t>(1, std::min<uint64_t>(want, fused ? fused_grid : (uint64_t)c->grid_max));
@@ -431,6 +434,8 @@ static int run_kernel(psg_ctx* c, KArgs& a, uint64_t count, psg_summary* out, bo
     void* params[] = {&a};
     HIPCHK(c, hipModuleLaunchKernel(fused, (unsigned)grid, 1, 1, (unsigned)threads_per_block(c->W), 1, 1, 0, c->stream,
                                     params, nullptr));
+  } else if (pack_g > 1) {  // (the packed launcher sizes its own grid: 4 waves x pack_g rows per block)
+    HIPCHK(c, launch_otr_packed(a, pack_g, c->stream));
   } else {
     HIPCHK(c, alg_row(c->cfg.alg)->launch(a, c->W, grid, c->stream));
   }
@@ -506,6 +511,16 @@ int psg_config_default(psg_config* cfg, int32_t alg, int32_t n) {
   return PSG_OK;
 }
 
+// The one rule of sub-wave packing (psg_subwave.hpp): G = 64 / P instances per wave, P the power
+// of two >= n, at least 4, for the algorithms that have a packed kernel (run_kernel asks here).
+int psg_pack_width(int32_t alg, int32_t n) {
+  if (!alg_row(alg) || n < 1 || n > PSG_MAX_N) return PSG_EINVAL;
+  if (alg != PSG_ALG_OTR || n > 32) return 1;
+  int P = 4;
+  while (P < n) P *= 2;
+  return 64 / P;
+}
+
 int psg_check_count(int32_t alg) {
   const AlgRow* row = alg_row(alg);
   return row ? row->checks.count : 0;
@@ -577,6 +592,7 @@ static int validate(const psg_config* cfg, std::string& m) {
   if (cfg->sched.drop_log2 > 16) { m = "drop_log2 > 16"; return PSG_EINVAL; }
   if (cfg->batch_capacity < 1) { m = "batch_capacity must be >= 1"; return PSG_EINVAL; }
   if (cfg->n_devices < 0 || cfg->n_devices > PSG_MAX_DEVICES) { m = "n_devices out of range 0..16"; return PSG_EINVAL; }
+  if (cfg->pack != 0 && cfg->pack != 1) { m = "pack must be 0 or 1"; return PSG_EINVAL; }
   return PSG_OK;
 }
 
@@ -798,7 +814,8 @@ static int multi_run(psg_ctx* c, uint64_t inst_begin, uint64_t count, const psg_
 // One launch over a whole batch from its staged inputs (seeded ones unless the caller staged this
 // range): psg_run_batch, and psg_run_batch_spec through a fused module's round kernel.
 static int run_whole_batch(psg_ctx* c, uint64_t inst_begin, uint64_t count, psg_summary* out,
-                           psg_instance_summary* per_inst, hipFunction_t fused = nullptr, uint64_t fused_grid = 0) {
+                           psg_instance_summary* per_inst, hipFunction_t fused = nullptr, uint64_t fused_grid = 0,
+                           bool packable = false) {
   if (!is_staged(c, inst_begin, count)) {
     int rc = psg_load_inputs(c, inst_begin, count, nullptr);
     if (rc) return rc;
@@ -815,7 +832,7 @@ static int run_whole_batch(psg_ctx* c, uint64_t inst_begin, uint64_t count, psg_
   a.out_decision = c->d_dec;
   a.out_dround = c->d_dround;
   a.out_inst = c->d_inst;
-  int rc = run_kernel(c, a, count, out, true, fused, fused_grid);
+  int rc = run_kernel(c, a, count, out, true, fused, fused_grid, packable);
   if (rc) return rc;
   c->last_count = count;
   if (per_inst) {
@@ -835,7 +852,7 @@ int psg_run_batch(psg_ctx* c, uint64_t inst_begin, uint64_t count, psg_summary* 
   }
   if (int rc = check_sched_range(c, inst_begin, count)) return rc;
   HIPCHK(c, hipSetDevice(c->cfg.device));
-  return run_whole_batch(c, inst_begin, count, out, per_inst);
+  return run_whole_batch(c, inst_begin, count, out, per_inst, nullptr, 0, /*packable=*/true);
 }
 
 static int validate_prog(const psg_spec_program* p, std::string& m) {

@@ -34,6 +34,8 @@ hipError_t launch_kset_es(const KArgs& a, int W, int grid, hipStream_t s);
 hipError_t launch_epsilon(const KArgs& a, int W, int grid, hipStream_t s);
 hipError_t launch_tpc(const KArgs& a, int W, int grid, hipStream_t s);
 hipError_t launch_lattice(const KArgs& a, int W, int grid, hipStream_t s);
+// OTR with G = psg_pack_width > 1 instances per wave (psg_otr_packed.hip); sizes its own grid
+hipError_t launch_otr_packed(const KArgs& a, int G, hipStream_t s);
 
 const void* otr_kernel_ptr(int W);
 const void* lv_kernel_ptr(int W);

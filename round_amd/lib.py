@@ -27,7 +27,7 @@ EXPORTED_SYMBOLS = [
     "psg_run_batch_spec", "psg_load_schedule", "psg_clear_schedule", "psg_materialize_schedule",
     "psg_population_fresh", "psg_population_next", "psg_population_read", "psg_spec_from_text", "psg_spec_release",
     "psg_spec_compile_native", "psg_spec_native_source", "psg_selftest_bitset", "psg_spec_rewrite_text",
-    "psg_spec_set_options",
+    "psg_spec_set_options", "psg_pack_width",
 ]
 
 
@@ -92,6 +92,7 @@ def load():
         L.psg_selftest_bitset.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32,
                                           C.POINTER(C.c_int32), C.c_int32]
         L.psg_spec_set_options.argtypes = [C.c_char_p]
+        L.psg_pack_width.argtypes = [C.c_int32, C.c_int32]
     except AttributeError:
         pass
     L.psg_spec_release.argtypes = [C.POINTER(abi.SpecProgram)]
@@ -100,6 +101,14 @@ def load():
                                         C.POINTER(C.c_int32)]
     _lib = L
     return L
+
+
+def pack_width(alg_id: int, n: int) -> int:
+    """psg_pack_width: instances per wave64 of a pack=True context (1: no packed kernel). Needs no device."""
+    w = load().psg_pack_width(alg_id, n)
+    if w < 1:
+        raise PsgError(w, f"psg_pack_width({alg_id}, {n})")
+    return w
 
 
 class Context:

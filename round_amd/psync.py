@@ -271,9 +271,12 @@ ALGORITHMS = {c.class_name: c for c in (OTR, LastVoting, FloodMin, KSetAgreement
 def make_config(alg: Algorithm, n: int, rounds: Optional[int] = None, seed: int = 1,
                 schedule: Optional[HOSchedule] = None, value_range: Optional[int] = None,
                 tiebreak: int = abi.PSG_TIE_CHAMP, device: int = 0,
-                batch_capacity: int = 1 << 20, devices: Optional[Sequence[int]] = None) -> abi.Config:
+                batch_capacity: int = 1 << 20, devices: Optional[Sequence[int]] = None,
+                pack: bool = False) -> abi.Config:
     """Build a psg_config (the reference's `new OTR(rt, ...)` + RTOptions). `devices`:
-    run every batch split over these HIP devices (one host thread each) instead of `device`."""
+    run every batch split over these HIP devices (one host thread each) instead of `device`.
+    `pack`: run small-n batches several instances per wave where the library has a packed
+    kernel (lib.pack_width > 1; the results are the same bit for bit)."""
     if not (1 <= n <= abi.PSG_MAX_N):
         raise ValueError(f"n={n} out of range 1..{abi.PSG_MAX_N}")
     c = abi.Config()
@@ -293,6 +296,7 @@ def make_config(alg: Algorithm, n: int, rounds: Optional[int] = None, seed: int 
     c.variant = alg.variant
     c.batch_capacity = batch_capacity
     c.sched = (schedule or alg.default_schedule(n)).to_c()
+    c.pack = 1 if pack else 0
     if devices:
         if len(devices) > abi.PSG_MAX_DEVICES:
             raise ValueError(f"at most {abi.PSG_MAX_DEVICES} devices per context")
@@ -341,11 +345,11 @@ class GpuRound:
     def __init__(self, alg: Algorithm, n: int, rounds: Optional[int] = None, seed: int = 1,
                  schedule: Optional[HOSchedule] = None, value_range: Optional[int] = None,
                  tiebreak: int = abi.PSG_TIE_CHAMP, device: int = 0, batch_capacity: int = 1 << 20,
-                 devices: Optional[Sequence[int]] = None):
+                 devices: Optional[Sequence[int]] = None, pack: bool = False):
         from . import lib
         self.alg = alg
         self.cfg = make_config(alg, n, rounds, seed, schedule, value_range, tiebreak, device, batch_capacity,
-                               devices)
+                               devices, pack)
         self._ctx = lib.Context(self.cfg)
 
     @property
