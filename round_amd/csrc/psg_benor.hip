@@ -396,7 +396,8 @@ PSG_DEV void benor_body(const KArgs& a) {
     sc.prep_good(0, g.lane, a.R);
     int32_t x0 = 0;
     if (g.valid) x0 = a.init ? init_x(a, i, inst, g.pid) : sc.init_value(g.pid, PSG_ALG_BENOR);
-    if constexpr (!SH::kFused) {
+    // (launch_w sends W > 1 seeded launches without a trace to benor_packed_kernel: none gets here)
+    if constexpr (!SH::kFused && (W == 1 || XHO)) {
       if (a.trace == nullptr) {  // built-in checker: one exchange per round
         benor_fast<W>(g, a, i, sc, cs, BX, x0, &bc);
         continue;

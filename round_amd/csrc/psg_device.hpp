@@ -414,10 +414,6 @@ PSG_DEV uint32_t xshfl(uint32_t v, int lane) {
     return (lane & 32) ? (uint32_t)r[0] : (uint32_t)r[1];
   }
 }
-template <int D>
-PSG_DEV uint64_t xshfl64(uint64_t v, int lane) {
-  return (uint64_t)xshfl<D>((uint32_t)v, lane) | ((uint64_t)xshfl<D>((uint32_t)(v >> 32), lane) << 32);
-}
 
 PSG_DEV uint32_t wave_or(uint32_t v) {
   v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, false);  // row_shr:1
@@ -622,10 +618,6 @@ struct Grp {
   uint64_t vmask;  // uniform: valid lanes of this wave
   uint64_t* xb;  // LDS: [2][W] ballot words
   int64_t* red;  // LDS: [2][W] reduction words
-
-  PSG_DEV void sync() const {
-    if constexpr (W > 1) __syncthreads();
-  }
 
   // LDS words of the ballot exchange (xb): two alternating regions of kFuse x W words,
   // so a region is rewritten only after the next barrier.
@@ -1665,19 +1657,12 @@ struct X0Set {
     return !g.any(mtest(need, g.pid) && !contains(v));
   }
 
-  // 1 unless v sits in one of its two home slots: 0 proves membership, 1 means
+  // Per value: 1 unless it sits in one of its two home slots: 0 proves membership, 1 means
   // "maybe not a member" (resolve with contains / all_in). The sentinel value itself
-  // always answers 1. (Exact in bitmap mode.)
+  // always answers 1. (Exact in bitmap mode.) Two values under one test of the mode (one
+  // scalar branch, not two).
   // (A branch-free form that computes both probes and selects one was measured 17 %
-  // slower on the OTR headline, gpurun_out ab10: the branch on the uniform mode is cheaper.)
-  PSG_DEV uint32_t maybe_out01(int32_t v) const {
-    if (bmode) return 1u - bm_in01(v);
-    const uint32_t h = slot(v);
-    const int32_t t0 = tab[h];
-    const int32_t t1 = tab[(h + 1) & (uint32_t)(kSlots - 1)];
-    return (ne01(t0, v) & ne01(t1, v)) | eq01(v, kEmpty);
-  }
-  // maybe_out01 of two values under one test of the mode (one scalar branch, not two)
+  // slower on the OTR headline: the branch on the uniform mode is cheaper.)
   PSG_DEV void maybe_out01_2(int32_t a, int32_t b, uint32_t& oa, uint32_t& ob) const {
     if (bmode) {
       oa = 1u - bm_in01(a);

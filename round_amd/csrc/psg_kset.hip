@@ -138,7 +138,7 @@ struct KsPk {
 };
 
 // The pre-round t staging ([word][pid], 8 KB at W = 4) is needed only in the few rounds before
-// every alive t is equal (tuni) — two or three of an instance's rounds — so the block's four
+// every alive t is equal — two or three of an instance's rounds — so the block's four
 // waves share two buffers (wave w uses buffer w / 2) under an LDS lock instead of owning one
 // each: 52 -> 36 KB of LDS per block, four blocks per CU instead of three.
 #ifndef PSG_KSET_STAGE_BUFS
@@ -184,14 +184,15 @@ PSG_DEV void pk_and_or(const Mask<W>& a, const Mask<W>& o, Mask<W>& all, Mask<W>
   }
 }
 
-// Hand-off to the uniform-t tail kernel (HAND, below). Header word of batch row i: bits 0-7 the
+// Hand-off to the uniform-t tail kernel (kset_tail_kernel, below). Header word of batch row i: bits 0-7 the
 // round the tail resumes at, bit 8 its deciders' "pick(t) is not an initial value", bit 9 "the
 // instance was finished here", bits 32-63 pick(t) of the common t. Per-lane word: bits 0-7 the
 // lane's Checks::ffv, 8-19 the flag word fw (decider bits 0-3, not-initial bits 8-11), 32-63 the
 // slots' halt rounds as bytes (0xFF = not halted). Decisions of halted processes in [row][n].
 constexpr uint64_t kHandDone = 1ull << 9;
 
-template <int W, bool HAND>
+// The general rounds of an instance: those before every alive process holds the same t.
+template <int W>
 PSG_DEV void kset_packed(const Pk<W>& P, const KArgs& a, uint64_t i, uint64_t inst, KsPk<W>& L, KsStage<W>& S,
                          int sbuf, int32_t* x0lds, BlockCounters* bc, PhaseTimers& pt) {
   const int n = a.n, kk = a.param;
@@ -250,14 +251,10 @@ PSG_DEV void kset_packed(const Pk<W>& P, const KArgs& a, uint64_t i, uint64_t in
     for (int j = 0; j < W; ++j) al[j] = P.val[j];
     act = P.ballot(al);
   }
-  // tuni: every alive process holds the same t. No round changes that (a merge's union and an
-  // adoption are that t again), so from the first round it holds on the staging, the round-0
-  // closed form and the classes / columns are skipped: same = |M|, t unchanged.
-  bool tuni = false;
-  const bool lazy = sc.drop == 0 && sc.ho_min < 0;  // crash-round survival words drawn on demand (below)
-  // HAND: the rounds from the first with every alive t equal (or with every process halted) run
-  // in kset_tail_kernel, whose live state fits twice the waves per SIMD; this kernel stores the
-  // state that kernel needs and leaves the instance.
+  // Once every alive process holds the same t, no round changes that (a merge's union and an
+  // adoption are that t again). The rounds from the first where it holds (or where every process
+  // has halted) run in kset_tail_kernel, whose live state fits twice the waves per SIMD; this
+  // kernel stores the state that kernel needs and leaves the instance.
   auto handoff = [&](int k, int32_t pu, uint32_t punot) {
     uint32_t hr = 0;
 #pragma unroll
@@ -271,314 +268,260 @@ PSG_DEV void kset_packed(const Pk<W>& P, const KArgs& a, uint64_t i, uint64_t in
     lds_sync<1>();  // x0s reads done before the next instance restages them
     pt.mark(3);
   };
+  // tuni: every alive t is equal. The round that finds it hands off and returns, so every test of
+  // it below reads false. The variable and the test around `closed` stay: without either, the
+  // compiler allocates this kernel's registers differently, and this kernel is benchmarked (C4).
+  bool tuni = false;
   for (int k = 0; k < a.R; ++k) {
-    // Once every process halted the state is frozen; the round has no step to take, but its
-    // check point is still evaluated (every counted process-round is checked).
-    const bool live = many(act);
-    if constexpr (HAND) {
-      if (!live) {
-        handoff(k, 0, 0u);
+    // Once every process halted the state is frozen; the rounds left have no step to take, but
+    // their check points are still evaluated (every counted process-round is checked): the tail's.
+    if (!many(act)) {
+      handoff(k, 0, 0u);
+      return;
+    }
+    Mask<W> goodS;
+    const bool good = sc.good_round(k, P.lane, a.R, goodS);
+    Mask<W> CB = mzero<W>(), CN = mzero<W>();
+    if (sc.crash_on) {
+#pragma unroll
+      for (int j = 0; j < W; ++j) {
+        CB.w[j] = __builtin_amdgcn_ballot_w64((uint32_t)cr[j] < (uint32_t)k);
+        CN.w[j] = __builtin_amdgcn_ballot_w64(cr[j] == k);
+      }
+    }
+    uint32_t dw[W];
+#pragma unroll
+    for (int j = 0; j < W; ++j) dw[j] = (fw >> j) & 1u;
+    const Mask<W> Dm = mand(P.ballot(dw), act);  // senders' decider flags (pre-state)
+    // round 0 (every alive sender still holds only its own origin): closed form below
+    bool closed = false;
+    if (!tuni) {
+      uint32_t notown[W];
+#pragma unroll
+      for (int j = 0; j < W; ++j) {
+        Mask<W> own = mzero<W>();
+        if (P.val[j]) own.w[j] = 1ull << P.lane;
+        notown[j] = meq(t[j], own) ? 0u : 1u;
+      }
+      closed = !many(mand(act, P.ballot(notown)));
+    }
+    // Every alive sender holding the same t (the common case once round 0 has spread the
+    // origins) is one compare per slot against the first alive sender's t (read from its
+    // lane) and a ballot; the instance is then handed to the tail.
+    if (!closed) {
+      const int q0 = mfirst(act), j0 = q0 >> 6, l0 = q0 & 63;
+      Mask<W> t0;
+#pragma unroll
+      for (int w = 0; w < W; ++w) {
+        t0.w[w] = readlane64(t[0].w[w], l0);
+#pragma unroll
+        for (int j = 1; j < W; ++j)
+          if (j0 == j) t0.w[w] = readlane64(t[j].w[w], l0);
+      }
+      uint32_t dif = 0;
+#pragma unroll
+      for (int j = 0; j < W; ++j) dif |= (uint32_t)((act.w[j] >> P.lane) & 1ull) & (meq(t[j], t0) ? 0u : 1u);
+      tuni = !pk_any(dif);
+      if (tuni) {  // every decision from here on is pick(t0); its X0 probe taken once
+        const int32_t pu = kset_pick<W>(t0, L.x0s, Emin, xmin);
+        handoff(k, pu, 1u - X0.contains01(pu));
         return;
       }
     }
-    if (live) {
-      Mask<W> goodS;
-      const bool good = sc.good_round(k, P.lane, a.R, goodS);
-      Mask<W> CB = mzero<W>(), CN = mzero<W>();
-      if (sc.crash_on) {
+    // the pre-round t masks staged for the class reads and adoptions ([word][pid])
+    const bool staged = !closed || many(Dm);
+    uint64_t* ts = nullptr;
+    if (staged) {
+      ts = S.acquire(sbuf, P.lane);
 #pragma unroll
-        for (int j = 0; j < W; ++j) {
-          CB.w[j] = __builtin_amdgcn_ballot_w64((uint32_t)cr[j] < (uint32_t)k);
-          CN.w[j] = __builtin_amdgcn_ballot_w64(cr[j] == k);
-        }
+      for (int j = 0; j < W; ++j)
+#pragma unroll
+        for (int w = 0; w < W; ++w) ts[w * 64 * W + P.pid(j)] = t[j].w[w];
+      lds_sync<1>();
+    }
+    // The classes of equal t among the alive senders (same = mailbox.filter(_._2._2 == t).size,
+    // uni = t ++ every received t) are the same for every receiver: found once per round (at
+    // most kClasses; the rest, rem, is walked sender by sender), their t and member masks kept
+    // in this wave's LDS, each slot's class index in cls (4 bits per slot, 15 = none). So the
+    // receivers need only the pre-round staging, not their own pre-round t, and each slot's t
+    // is updated in place (no second set of W x W mask words per lane).
+    //
+    // Column form (the common case, few origins vary): I = the origins every alive sender
+    // holds, U = those some alive sender holds, D = U \ I the varying ones. Every alive t is
+    // I + (t & D), so for a receiver p (alive, M its senders, all alive)
+    //   uni  = t_p + {o in D : M meets H_o}                 H_o = {alive q : o in t_q}
+    //   same = |M & Eq_p|,  Eq_p = AND over o in D of (o in t_p ? H_o : not H_o)
+    // — |D| column steps per slot instead of a walk over the senders or their classes.
+    int ncls = 0, ncols = 0;
+    uint32_t cls = 0xFFFFu;
+    Mask<W> rem = act, D = mzero<W>();
+    const bool cols = !closed;
+    if (cols) {
+      Mask<W> il, ul;
+#pragma unroll
+      for (int w = 0; w < W; ++w) {
+        il.w[w] = ~0ull;
+        ul.w[w] = 0ull;
       }
-      uint32_t dw[W];
-#pragma unroll
-      for (int j = 0; j < W; ++j) dw[j] = (fw >> j) & 1u;
-      const Mask<W> Dm = mand(P.ballot(dw), act);  // senders' decider flags (pre-state)
-      // round 0 (every alive sender still holds only its own origin): closed form below
-      bool closed = false;
-      if (!tuni) {
-        uint32_t notown[W];
-#pragma unroll
-        for (int j = 0; j < W; ++j) {
-          Mask<W> own = mzero<W>();
-          if (P.val[j]) own.w[j] = 1ull << P.lane;
-          notown[j] = meq(t[j], own) ? 0u : 1u;
-        }
-        closed = !many(mand(act, P.ballot(notown)));
-      }
-      // Every alive sender holding the same t (the common case once round 0 has spread the
-      // origins) is one compare per slot against the first alive sender's t (read from its
-      // lane) and a ballot; then tuni holds for the rest of the instance.
-      if (!tuni && !closed) {
-        const int q0 = mfirst(act), j0 = q0 >> 6, l0 = q0 & 63;
-        Mask<W> t0;
-#pragma unroll
-        for (int w = 0; w < W; ++w) {
-          t0.w[w] = readlane64(t[0].w[w], l0);
-#pragma unroll
-          for (int j = 1; j < W; ++j)
-            if (j0 == j) t0.w[w] = readlane64(t[j].w[w], l0);
-        }
-        uint32_t dif = 0;
-#pragma unroll
-        for (int j = 0; j < W; ++j) dif |= (uint32_t)((act.w[j] >> P.lane) & 1ull) & (meq(t[j], t0) ? 0u : 1u);
-        tuni = !pk_any(dif);
-        if constexpr (HAND) {
-          if (tuni) {  // every decision from here on is pick(t0); its X0 probe taken once
-            const int32_t pu = kset_pick<W>(t0, L.x0s, Emin, xmin);
-            handoff(k, pu, 1u - X0.contains01(pu));
-            return;
-          }
-        }
-      }
-      // the pre-round t masks staged for the class reads and adoptions ([word][pid])
-      const bool staged = !tuni && (!closed || many(Dm));
-      uint64_t* ts = nullptr;
-      if (staged) {
-        ts = S.acquire(sbuf, P.lane);
-#pragma unroll
-        for (int j = 0; j < W; ++j)
-#pragma unroll
-          for (int w = 0; w < W; ++w) ts[w * 64 * W + P.pid(j)] = t[j].w[w];
-        lds_sync<1>();
-      }
-      // The classes of equal t among the alive senders (same = mailbox.filter(_._2._2 == t).size,
-      // uni = t ++ every received t) are the same for every receiver: found once per round (at
-      // most kClasses; the rest, rem, is walked sender by sender), their t and member masks kept
-      // in this wave's LDS, each slot's class index in cls (4 bits per slot, 15 = none). So the
-      // receivers need only the pre-round staging, not their own pre-round t, and each slot's t
-      // is updated in place (no second set of W x W mask words per lane).
-      //
-      // Column form (the common case, few origins vary): I = the origins every alive sender
-      // holds, U = those some alive sender holds, D = U \ I the varying ones. Every alive t is
-      // I + (t & D), so for a receiver p (alive, M its senders, all alive)
-      //   uni  = t_p + {o in D : M meets H_o}                 H_o = {alive q : o in t_q}
-      //   same = |M & Eq_p|,  Eq_p = AND over o in D of (o in t_p ? H_o : not H_o)
-      // — |D| column steps per slot instead of a walk over the senders or their classes.
-      int ncls = 0, ncols = 0;
-      uint32_t cls = 0xFFFFu;
-      Mask<W> rem = act, D = mzero<W>();
-      const bool cols = !tuni && !closed;
-      if (cols) {
-        Mask<W> il, ul;
-#pragma unroll
-        for (int w = 0; w < W; ++w) {
-          il.w[w] = ~0ull;
-          ul.w[w] = 0ull;
-        }
-#pragma unroll
-        for (int j = 0; j < W; ++j) {
-          const bool s = (act.w[j] >> P.lane) & 1ull;
-#pragma unroll
-          for (int w = 0; w < W; ++w) {
-            il.w[w] &= s ? t[j].w[w] : ~0ull;
-            ul.w[w] |= s ? t[j].w[w] : 0ull;
-          }
-        }
-        Mask<W> I, U;
-        pk_and_or<W>(il, ul, I, U);
-        D = mandn(U, I);
-        ncols = mpopc(D);
-      }
-      const bool colform = cols && ncols <= KsPk<W>::kCols;
-      if (colform) {
-        Mask<W> dd = D;
-        for (int c = 0; c < ncols; ++c) {
-          const int o = mtake_first(dd);
-          uint32_t hb[W];
-#pragma unroll
-          for (int j = 0; j < W; ++j) hb[j] = mtest(t[j], o) ? 1u : 0u;
-          const Mask<W> H = mand(P.ballot(hb), act);
-#pragma unroll
-          for (int w = 0; w < W; ++w)
-            if (P.lane == w) L.hol[c][w] = H.w[w];
-        }
-        lds_sync<1>();
-      } else if (cols) {
-        for (; ncls < KsPk<W>::kClasses && many(rem); ++ncls) {
-          const Mask<W> tq = load_t<W, 64 * W>(ts, mfirst(rem));
-          uint32_t mine[W];
-#pragma unroll
-          for (int jj = 0; jj < W; ++jj) {
-            mine[jj] = meq(t[jj], tq) ? 1u : 0u;
-            if (mine[jj] && ((cls >> (4 * jj)) & 15u) == 15u) cls = (cls & ~(15u << (4 * jj))) | ((uint32_t)ncls << (4 * jj));
-          }
-          const Mask<W> E = mand(P.ballot(mine), rem);
-          rem = mandn(rem, E);
-          if (P.lane < W) {  // uniform values: lane w stores word w
-#pragma unroll
-            for (int w = 0; w < W; ++w)
-              if (P.lane == w) {
-                L.ct[ncls][w] = tq.w[w];
-                L.ce[ncls][w] = E.w[w];
-              }
-          }
-        }
-        lds_sync<1>();
-      }
-      pt.mark(1);
-      pt.add(0, 1);  // event-count builds: round paths (live, closed, uniform t, columns, classes)
-      pt.add(1, closed);
-      pt.add(2, tuni);
-      pt.add(3, colform);
-      pt.add(4, colform ? ncols : 0);
-      pt.add(5, cols && !colform);
-      pt.add(6, cols && !colform ? mpopc(rem) : 0);
-      pt.add(7, many(CN));
-      // one slot at a time (its HO set M, its merge or adoption)
-      if (!HAND && tuni) {
-        // Every sender's t is t_p, so a step reads its mailbox only through hc (some decider
-        // heard) and same = |M| > need (KSetAgreement.scala:46-58), and t never changes (a
-        // union or an adoption is t_p again). In a crash round (no benign loss, no ho_min) M
-        // lies between Mlo (every crashing sender's message lost) and Mhi (all delivered); when
-        // both bounds give the same hc and |M| > need for every live slot of the wave, the
-        // round's survival words change nothing and are not drawn (each is a pure function of
-        // (instance, round, pid): skipping one moves no other draw).
-        const bool lazyr = lazy && many(CN);
-#pragma unroll
-        for (int j = 0; j < W; ++j) {
-          const bool halted = halt_round[j] >= 0;
-          const uint32_t decider = (fw >> j) & 1u;
-          const uint32_t live = P.val[j] & (halted ? 0u : 1u) & (1u - decider);
-          uint32_t hc, big;
-          bool exact = !lazyr;
-          if (lazyr) {
-            uint64_t one[W], zero[W];
-#pragma unroll
-            for (int w = 0; w < W; ++w) {
-              one[w] = ~0ull;
-              zero[w] = 0ull;
-            }
-            const Mask<W> Mhi = mand(sc.assemble(P.pid(j), good, goodS, CB, CN, one, one), act);
-            const Mask<W> Mlo = mand(sc.assemble(P.pid(j), good, goodS, CB, CN, one, zero), act);
-            const uint32_t hlo = many(mand(Mlo, Dm)) ? 1u : 0u, hhi = many(mand(Mhi, Dm)) ? 1u : 0u;
-            const uint32_t plo = mpopc(Mlo) > need ? 1u : 0u, phi = mpopc(Mhi) > need ? 1u : 0u;
-            hc = hlo;
-            big = plo;
-            // undetermined: hc open, or no decider heard for sure and |M| > need open
-            exact = pk_any(live & ((hlo ^ hhi) | ((1u - hlo) & (plo ^ phi))));
-          }
-          if (exact) {
-            const Mask<W> M = mand(sc.ho(k, P.pid(j), good, goodS, CB, CN), act);
-            hc = many(mand(M, Dm)) ? 1u : 0u;
-            big = mpopc(M) > need ? 1u : 0u;
-          }
-          pt.mark(6);  // (profiling builds: t6 = the slots' HO sets)
-          if (!halted && decider) {  // decide(pick(t)); exitAtEndOfRound (KSetAgreement.scala:48-50)
-            const int32_t v = kset_pick<W>(t[j], L.x0s, Emin, xmin);
-            decision[j] = v;
-            fw |= (1u - X0.contains01(v)) << (8 + j);
-            halt_round[j] = k;
-          }
-          fw |= (live & (hc | big)) << j;  // adopts, or merges with same > n - k: decider
-          pt.mark(2);
-        }
-      } else {
-#pragma unroll
-        for (int j = 0; j < W; ++j) {
-          uint32_t becomeDec = 0;
-          const bool halted = halt_round[j] >= 0;  // before this round (set below when it decides)
-          const uint32_t decider = (fw >> j) & 1u;
-          const Mask<W> M = mand(sc.ho(k, P.pid(j), good, goodS, CB, CN), act);
-          pt.mark(6);
-          const uint32_t live = P.val[j] & (halted ? 0u : 1u) & (1u - decider);
-          const uint32_t hc = many(mand(M, Dm)) ? 1u : 0u;
-          const uint32_t adopt = live & hc, mergep = live & (1u - hc);
-          Mask<W> tnew = t[j];
-          if (pk_any(mergep)) {
-            int same = 0;
-            Mask<W> uni = t[j];
-            if (closed) {
-              same = ((M.w[j] >> P.lane) & 1ull) ? 1 : 0;
-              uni = mor(t[j], M);
-            } else if (colform) {
-              Mask<W> Eq = act, dd = D;
-              for (int c = 0; c < ncols; ++c) {
-                const int o = mtake_first(dd);
-                Mask<W> H;
-#pragma unroll
-                for (int w = 0; w < W; ++w) H.w[w] = L.hol[c][w];
-                const bool hit = many(mand(M, H));
-                const uint64_t bit = 1ull << (o & 63);
-                const bool mine = mtest(t[j], o);
-#pragma unroll
-                for (int w = 0; w < W; ++w) {
-                  uni.w[w] |= (hit && (o >> 6) == w) ? bit : 0ull;
-                  Eq.w[w] &= mine ? H.w[w] : ~H.w[w];
-                }
-              }
-              same = mpopc(mand(M, Eq));
-            } else {
-              const int mc = (int)((cls >> (4 * j)) & 15u);
-              for (int c = 0; c < ncls; ++c) {
-                Mask<W> E, tq;
-#pragma unroll
-                for (int w = 0; w < W; ++w) {
-                  E.w[w] = L.ce[c][w];
-                  tq.w[w] = L.ct[c][w];
-                }
-                const Mask<W> ME = mand(M, E);
-                if (c == mc) same = mpopc(ME);
-                if (many(ME)) uni = mor(uni, tq);
-              }
-              Mask<W> rr = rem;
-              while (many(rr)) {
-                const int q = mtake_first(rr);
-                const Mask<W> tq = load_t<W, 64 * W>(ts, q);
-                if (mtest(M, q)) {
-                  same += meq(tq, t[j]) ? 1 : 0;
-                  uni = mor(uni, tq);
-                }
-              }
-            }
-            if (mergep) {
-              if (same > need) becomeDec = 1;
-              else tnew = uni;
-            }
-          }
-          if (adopt) {  // t = content.find(_._1).get._2 — last decider message in iteration order
-            tnew = load_t<W, 64 * W>(ts, kset_find<W, 64 * W>(a, ts, M, mand(M, Dm), colform ? L.hol : nullptr, ncols));
-            becomeDec = 1;
-          }
-          if (!halted && decider) {  // decide(pick(t)); exitAtEndOfRound (KSetAgreement.scala:48-50)
-            const int32_t v = kset_pick<W>(t[j], L.x0s, Emin, xmin);
-            decision[j] = v;
-            fw |= (1u - X0.contains01(v)) << (8 + j);
-            halt_round[j] = k;
-          }
-          if (!halted) {  // the post-round state of slot j (its pre-round t is in the staging)
-            t[j] = tnew;
-            fw |= becomeDec << j;
-          }
-          pt.mark(2);
-        }
-      }
-      if (staged) S.release(sbuf, P.lane);  // all reads of ts (and hol / ct / ce) done
-      uint32_t al[W];
 #pragma unroll
       for (int j = 0; j < W; ++j) {
-        al[j] = P.val[j] & (halt_round[j] >= 0 ? 0u : 1u);
+        const bool s = (act.w[j] >> P.lane) & 1ull;
+#pragma unroll
+        for (int w = 0; w < W; ++w) {
+          il.w[w] &= s ? t[j].w[w] : ~0ull;
+          ul.w[w] |= s ? t[j].w[w] : 0ull;
+        }
       }
-      act = P.ballot(al);
+      Mask<W> I, U;
+      pk_and_or<W>(il, ul, I, U);
+      D = mandn(U, I);
+      ncols = mpopc(D);
+    }
+    const bool colform = cols && ncols <= KsPk<W>::kCols;
+    if (colform) {
+      Mask<W> dd = D;
+      for (int c = 0; c < ncols; ++c) {
+        const int o = mtake_first(dd);
+        uint32_t hb[W];
+#pragma unroll
+        for (int j = 0; j < W; ++j) hb[j] = mtest(t[j], o) ? 1u : 0u;
+        const Mask<W> H = mand(P.ballot(hb), act);
+#pragma unroll
+        for (int w = 0; w < W; ++w)
+          if (P.lane == w) L.hol[c][w] = H.w[w];
+      }
+      lds_sync<1>();
+    } else if (cols) {
+      for (; ncls < KsPk<W>::kClasses && many(rem); ++ncls) {
+        const Mask<W> tq = load_t<W, 64 * W>(ts, mfirst(rem));
+        uint32_t mine[W];
+#pragma unroll
+        for (int jj = 0; jj < W; ++jj) {
+          mine[jj] = meq(t[jj], tq) ? 1u : 0u;
+          if (mine[jj] && ((cls >> (4 * jj)) & 15u) == 15u) cls = (cls & ~(15u << (4 * jj))) | ((uint32_t)ncls << (4 * jj));
+        }
+        const Mask<W> E = mand(P.ballot(mine), rem);
+        rem = mandn(rem, E);
+        if (P.lane < W) {  // uniform values: lane w stores word w
+#pragma unroll
+          for (int w = 0; w < W; ++w)
+            if (P.lane == w) {
+              L.ct[ncls][w] = tq.w[w];
+              L.ce[ncls][w] = E.w[w];
+            }
+        }
+      }
+      lds_sync<1>();
+    }
+    pt.mark(1);
+    pt.add(0, 1);  // event-count builds: round paths (live, closed, columns, classes; slot 2 unused)
+    pt.add(1, closed);
+    pt.add(3, colform);
+    pt.add(4, colform ? ncols : 0);
+    pt.add(5, cols && !colform);
+    pt.add(6, cols && !colform ? mpopc(rem) : 0);
+    pt.add(7, many(CN));
+    // one slot at a time (its HO set M, its merge or adoption)
+#pragma unroll
+    for (int j = 0; j < W; ++j) {
+      uint32_t becomeDec = 0;
+      const bool halted = halt_round[j] >= 0;  // before this round (set below when it decides)
+      const uint32_t decider = (fw >> j) & 1u;
+      const Mask<W> M = mand(sc.ho(k, P.pid(j), good, goodS, CB, CN), act);
+      pt.mark(6);
+      const uint32_t live = P.val[j] & (halted ? 0u : 1u) & (1u - decider);
+      const uint32_t hc = many(mand(M, Dm)) ? 1u : 0u;
+      const uint32_t adopt = live & hc, mergep = live & (1u - hc);
+      Mask<W> tnew = t[j];
+      if (pk_any(mergep)) {
+        int same = 0;
+        Mask<W> uni = t[j];
+        if (closed) {
+          same = ((M.w[j] >> P.lane) & 1ull) ? 1 : 0;
+          uni = mor(t[j], M);
+        } else if (colform) {
+          Mask<W> Eq = act, dd = D;
+          for (int c = 0; c < ncols; ++c) {
+            const int o = mtake_first(dd);
+            Mask<W> H;
+#pragma unroll
+            for (int w = 0; w < W; ++w) H.w[w] = L.hol[c][w];
+            const bool hit = many(mand(M, H));
+            const uint64_t bit = 1ull << (o & 63);
+            const bool mine = mtest(t[j], o);
+#pragma unroll
+            for (int w = 0; w < W; ++w) {
+              uni.w[w] |= (hit && (o >> 6) == w) ? bit : 0ull;
+              Eq.w[w] &= mine ? H.w[w] : ~H.w[w];
+            }
+          }
+          same = mpopc(mand(M, Eq));
+        } else {
+          const int mc = (int)((cls >> (4 * j)) & 15u);
+          for (int c = 0; c < ncls; ++c) {
+            Mask<W> E, tq;
+#pragma unroll
+            for (int w = 0; w < W; ++w) {
+              E.w[w] = L.ce[c][w];
+              tq.w[w] = L.ct[c][w];
+            }
+            const Mask<W> ME = mand(M, E);
+            if (c == mc) same = mpopc(ME);
+            if (many(ME)) uni = mor(uni, tq);
+          }
+          Mask<W> rr = rem;
+          while (many(rr)) {
+            const int q = mtake_first(rr);
+            const Mask<W> tq = load_t<W, 64 * W>(ts, q);
+            if (mtest(M, q)) {
+              same += meq(tq, t[j]) ? 1 : 0;
+              uni = mor(uni, tq);
+            }
+          }
+        }
+        if (mergep) {
+          if (same > need) becomeDec = 1;
+          else tnew = uni;
+        }
+      }
+      if (adopt) {  // t = content.find(_._1).get._2 — last decider message in iteration order
+        tnew = load_t<W, 64 * W>(ts, kset_find<W, 64 * W>(a, ts, M, mand(M, Dm), colform ? L.hol : nullptr, ncols));
+        becomeDec = 1;
+      }
+      if (!halted && decider) {  // decide(pick(t)); exitAtEndOfRound (KSetAgreement.scala:48-50)
+        const int32_t v = kset_pick<W>(t[j], L.x0s, Emin, xmin);
+        decision[j] = v;
+        fw |= (1u - X0.contains01(v)) << (8 + j);
+        halt_round[j] = k;
+      }
+      if (!halted) {  // the post-round state of slot j (its pre-round t is in the staging)
+        t[j] = tnew;
+        fw |= becomeDec << j;
+      }
       pt.mark(2);
     }
+    if (staged) S.release(sbuf, P.lane);  // all reads of ts (and hol / ct / ce) done
+    uint32_t al[W];
+#pragma unroll
+    for (int j = 0; j < W; ++j) {
+      al[j] = P.val[j] & (halt_round[j] >= 0 ? 0u : 1u);
+    }
+    act = P.ballot(al);
+    pt.mark(2);
     check(k + 1);
-    pt.mark(live ? 4 : 5);
+    pt.mark(4);
   }
+  // R rounds without a hand-off: the instance is finished here
   int32_t mainx[W];
 #pragma unroll
   for (int j = 0; j < W; ++j) mainx[j] = P.val[j] ? kset_pick<W>(t[j], L.x0s, Emin, xmin) : 0;
   pk_finish<W>(P, a, i, ck, kKAgreeChecks, decision, halt_round, halt_round, mainx, bc);
-  if constexpr (HAND) {
-    if (P.lane == 0) a.hand_hdr[i] = kHandDone;
-  }
+  if (P.lane == 0) a.hand_hdr[i] = kHandDone;
   lds_sync<1>();  // x0s reads done before the next instance restages them
   pt.mark(3);
 }
 
-// The uniform-t tail of a handed-off instance (kset_packed<W, true>): every alive process holds
+// The uniform-t tail of a handed-off instance (kset_packed): every alive process holds
 // the same t (or none is alive), so no round changes any t (a union of equal t's and an adoption
 // are that t), every decision is pick(t) = pu, and a step reads its mailbox only through hc (some
 // decider heard) and |M| > n - k (KSetAgreement.scala:46-58). The lane keeps its slots' decision,
@@ -740,10 +683,7 @@ PSG_DEV void kset_tail(const Pk<W>& P, const KArgs& a, uint64_t i, uint64_t inst
 #ifndef PSG_KSET_PK_WPE
 #define PSG_KSET_PK_WPE 3  // W = 4: four 256-bit t masks per lane; 2 -> 3 after the per-slot state diet: C4 f=1 2.80 -> 2.18 ms
 #endif
-#ifndef PSG_KSET_SPLIT
-#define PSG_KSET_SPLIT 1  // 1: general rounds here, the uniform-t tail in kset_tail_kernel; 0: one kernel
-#endif
-template <int W, bool HAND>
+template <int W>
 __global__ void __launch_bounds__(64 * KsStage<W>::kWaves) __attribute__((amdgpu_waves_per_eu(PSG_KSET_PK_WPE)))
 kset_packed_kernel(KArgs a) {
   static_assert(64 * KsStage<W>::kWaves == 256, "launched with 256-thread blocks (launch_w)");
@@ -757,12 +697,12 @@ kset_packed_kernel(KArgs a) {
   Pk<W> P;
   P.setup(a.n);
   const int grp = threadIdx.x >> 6;
-  PhaseTimers pt;  // profiling builds only: t0 setup, t1 staging + classes, t2 slot updates, t3 finish,
-  pt.start();      // t4 check after a live round, t5 frozen round, t6 the slots' HO sets
+  PhaseTimers pt;  // profiling builds only: t0 setup, t1 staging + classes, t2 slot updates, t3 finish or hand-off,
+  pt.start();      // t4 check after a round, t6 the slots' HO sets
   InstanceQueue<1> Q;
   for (uint64_t i = Q.take(a); i != Q.kDone; i = Q.take(a))
-    kset_packed<W, HAND>(P, a, i, instance_id(a, i), L[grp], S, grp * KsStage<W>::kBufs / KsStage<W>::kWaves, x0tab[grp],
-                         &bc, pt);
+    kset_packed<W>(P, a, i, instance_id(a, i), L[grp], S, grp * KsStage<W>::kBufs / KsStage<W>::kWaves, x0tab[grp], &bc,
+                   pt);
   pt.flush(a.counters, P.lane);
   __syncthreads();
   counters_flush(&bc, a.counters, kKAgreeChecks, a.R);
@@ -963,14 +903,12 @@ kset_kernel(KArgs a) {
 template <int W>
 static hipError_t launch_w(const KArgs& a, int grid, hipStream_t s) {
   if constexpr (W > 1) {  // seeded schedule, built-in checker: lane-packed path
-    if (!a.ho_in && !a.trace) {
-      if (PSG_KSET_SPLIT && a.hand_hdr) {  // general rounds, then the uniform-t tail (same stream)
-        if (hipError_t e = launch_pk<PSG_ALG_KSET, W>(kset_packed_kernel<W, true>, a, s)) return e;
-        if (a.drop_log2 == 0 && a.ho_min < 0)  // loss-free schedules: uniform mailboxes but crash rounds
-          return launch_pk<PSG_ALG_KSET | 0x100, W>(kset_tail_kernel<W, true>, a, s);
-        return launch_pk<PSG_ALG_KSET | 0x300, W>(kset_tail_kernel<W, false>, a, s);
-      }
-      return launch_pk<PSG_ALG_KSET | 0x200, W>(kset_packed_kernel<W, false>, a, s);
+    if (!a.ho_in && !a.trace) {  // general rounds, then the uniform-t tail (same stream)
+      if (!a.hand_hdr) return hipErrorInvalidValue;  // (psg_create allocates the hand-off buffer for every W > 1)
+      if (hipError_t e = launch_pk<PSG_ALG_KSET, W>(kset_packed_kernel<W>, a, s)) return e;
+      if (a.drop_log2 == 0 && a.ho_min < 0)  // loss-free schedules: uniform mailboxes but crash rounds
+        return launch_pk<PSG_ALG_KSET | 0x100, W>(kset_tail_kernel<W, true>, a, s);
+      return launch_pk<PSG_ALG_KSET | 0x300, W>(kset_tail_kernel<W, false>, a, s);
     }
   }
   if (a.ho_in) return launch_grp<W>(kset_kernel<W, true>, a, grid, s);

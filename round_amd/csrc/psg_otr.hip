@@ -202,17 +202,10 @@ PSG_DEV void otr_check_initial(Grp<1>& g, Checks& ck, int n, int32_t x, uint32_t
   ck.record(fb, false, 0, g.lane);
 }
 
-// The W == 1 forms of the per-instance setup and finish, each behind a bit for A/B builds
-// (-DPSG_OTR_SF=mask): 1 X0Set::build_window, 2 otr_check_initial, 4 finish_instance_w1
-// with the WaveTally. W > 1 keeps the general forms.
-#ifndef PSG_OTR_SF
-#define PSG_OTR_SF 7
-#endif
-template <int W>
-PSG_DEV constexpr bool kSF(int bit) { return W == 1 && (PSG_OTR_SF & bit) != 0; }
-
 // Kernel body; SH: the Spec hook (NoHook in psg_device.hpp). TR = false: the launch has no
 // Spec-program trace (a.trace == nullptr), known at compile time.
+// W == 1 takes its own forms of the per-instance setup and finish: X0Set::build_window,
+// otr_check_initial, and finish_instance_w1 with the WaveTally. W > 1 keeps the general forms.
 template <int W, bool V2, bool XHO, class SH = NoHook, bool TR = true>
 PSG_DEV void otr_body(const KArgs& a) {
   const bool tracing_on = SH::kFused || (TR && a.trace != nullptr);
@@ -262,7 +255,7 @@ PSG_DEV void otr_body(const KArgs& a) {
     if (g.valid) x0 = a.init ? x0host : sc.init_value(g.pid, PSG_ALG_OTR);
     pt.mark(5);
     X0Set<W> X0;
-    if constexpr (kSF<W>(1)) X0.build_window(g, x0tab[grp], x0, a.V);
+    if constexpr (W == 1) X0.build_window(g, x0tab[grp], x0, a.V);
     else X0.build(g, x0tab[grp], x0);
     pt.mark(6);
     // OtrProcess state after init(io) (Otr.scala:15-26); flags are 0/1 lane words
@@ -275,7 +268,7 @@ PSG_DEV void otr_body(const KArgs& a) {
     ck.reset();
     typename SH::template State<W> sh(g, grp, n);  // fused Spec evaluation state (NoHook: empty)
     if constexpr (!SH::kFused) {
-      if constexpr (kSF<W>(2)) otr_check_initial<V2>(g, ck, n, x, valid01);
+      if constexpr (W == 1) otr_check_initial<V2>(g, ck, n, x, valid01);
       else otr_check<W, V2>(g, L, X0, ck, 0, false, n, full, x, dec01, decision, 0u, -1, valid01, od, ox, ckthr);
     }
     // OTR2's decision is an Option (PSG_NONE32 when empty)
@@ -414,7 +407,7 @@ PSG_DEV void otr_body(const KArgs& a) {
       pt.mark(2);
     }
     pt.add(6, 1u);  // event build: instances
-    if constexpr (kSF<W>(4))
+    if constexpr (W == 1)
       finish_instance_w1(g, a, i, hook_checks<SH>(sh, ck), hook_slots<SH>(kOtrChecks), dec_val, dec_round, halt_round, x,
                          &bc, &tally, &wtally, live_rounds, &pt);
     else
@@ -424,7 +417,7 @@ PSG_DEV void otr_body(const KArgs& a) {
   }
   pt.flush(a.counters, threadIdx.x & 63);
   tally.flush(&bc);
-  if constexpr (kSF<W>(4)) wtally.flush(&bc, hook_slots<SH>(kOtrChecks));
+  if constexpr (W == 1) wtally.flush(&bc, hook_slots<SH>(kOtrChecks));
   __syncthreads();
   counters_flush(&bc, a.counters, hook_slots<SH>(kOtrChecks), a.R);
 }

@@ -26,12 +26,13 @@ cells left to another module name the test (`DELEGATED`).
 
 Findings written down while building the table:
 
-* KSetAgreement's unsplit launch shape (`kset_packed_kernel<W, false>`, psg_kset.hip launch_w)
-  cannot be reached through the C ABI: psg_create allocates the hand-off buffer for every
-  KSetAgreement context with W > 1 (psg_api.hip, `d_hand.grow`), make_args always sets
-  `hand_hdr` from it, and PSG_KSET_SPLIT is 1 in the committed build. The two reachable shapes
-  are general rounds + loss-free tail (`drop_log2 == 0 && ho_min < 0`: rows "kset") and general
-  rounds + general tail (rows "kset-loss" by drop_log2 > 0 and "kset-homin" by ho_min >= 0).
+* KSetAgreement once had a third, unsplit launch shape (one lane-packed kernel for all rounds) that
+  could not be reached through the C ABI: psg_create allocates the hand-off buffer for every
+  KSetAgreement context with W > 1 (psg_api.hip, `d_hand.grow`) and make_args always sets
+  `hand_hdr` from it. That shape has been deleted; launch_w (psg_kset.hip) refuses a W > 1 seeded
+  launch without the buffer. The two shapes are general rounds + loss-free tail
+  (`drop_log2 == 0 && ho_min < 0`: rows "kset") and general rounds + general tail (rows
+  "kset-loss" by drop_log2 > 0 and "kset-homin" by ho_min >= 0).
 * The FloodMin mutant (variant 1: decides from round f - 1 on) and the KSetAgreement mutant
   (variant 1: `same > 1` instead of `same > n - k`) decide early, but still a value some process
   held, and every held value is a minimum of initial values: neither can decide a value that is not
@@ -100,20 +101,23 @@ def dispatch(alg, n, sched, mode):
        `psg_fused_a<alg>_w<W>`, or `psg_fused_x_a<alg>_w<W>` when a schedule is loaded
        (psg_api.hip:958-971).
     2. explicit (`a.ho_in != 0`): `*_kernel<W, true>` for every algorithm. The lane-packed branches
-       test `!a.ho_in` first (psg_otr.hip:444, psg_lv.hip:429, psg_slv.hip:229, psg_tpc.hip:164,
-       psg_epsilon.hip:525, psg_benor.hip:513, psg_kset_es.hip:326, psg_kset.hip:976,
-       psg_floodmin.hip:435).
+       test `!a.ho_in` first (psg_otr.hip:437, psg_lv.hip:429, psg_slv.hip:229, psg_tpc.hip:136,
+       psg_epsilon.hip:525, psg_benor.hip:514, psg_kset_es.hip:326, psg_kset.hip:914,
+       psg_floodmin.hip:375).
     3. traced (`a.trace != 0`): the group kernel `*_kernel<W, false>`; OTR / OTR2 / LastVoting /
-       ShortLastVoting / TwoPhaseCommit have a branch of their own for it (psg_otr.hip:445,
-       psg_lv.hip:430, psg_slv.hip:230, psg_tpc.hip:165), the others fall through their packed
+       ShortLastVoting / TwoPhaseCommit have a branch of their own for it (psg_otr.hip:438,
+       psg_lv.hip:430, psg_slv.hip:230, psg_tpc.hip:137), the others fall through their packed
        test `!a.trace` to the last line of launch_w.
-    4. seeded, W > 1, BenOr / KSetEarlyStopping: the lane-packed kernel (psg_benor.hip:510-511,
+    4. seeded, W > 1, BenOr / KSetEarlyStopping: the lane-packed kernel (psg_benor.hip:511-512,
        psg_kset_es.hip:323-324).
     5. seeded, W > 1, KSetAgreement: lane-packed general rounds, then the uniform-t tail, loss-free
-       when `drop_log2 == 0 && ho_min < 0`, else general (psg_kset.hip:965-972); FloodMin when the
-       schedule is crash-only, `drop_log2 == 0 && good_p32 == 0 && ho_min < 0`
-       (psg_floodmin.hip:431-433).
+       when `drop_log2 == 0 && ho_min < 0`, else general (psg_kset.hip:905-911; a context without
+       the hand-off buffer gets hipErrorInvalidValue, line 907); FloodMin when the schedule is
+       crash-only, `drop_log2 == 0 && good_p32 == 0 && ho_min < 0` (psg_floodmin.hip:371-373).
     6. everything else: the group kernel `*_kernel<W, false>` (the last line of every launch_w).
+       For FloodMin and BenOr at W > 1 that is a lossy (FloodMin) or traced launch only, so those
+       six kernels hold no built-in-check fast arm (floodmin_fast is W == 1; benor_fast is compiled
+       for W == 1 and for the explicit-schedule kernels).
     """
     W = (n + 63) // 64
     if mode in ("fused", "fused-x"):
