@@ -1226,15 +1226,126 @@ struct Inst {
   CrashSets<W> cs;  // per-instance crash rounds (no per-round exchange for W > 1)
   // crl: 64*W words of LDS (W > 1); call from uniform control flow
   PSG_DEV void begin(Grp<W>& g, const KArgs& a, uint64_t i, int32_t* crl) {
+    begin_front(g, a, i, crl);
+    sc.prep_good(0, g.lane, a.R);
+  }
+  // begin() without the first block of good rounds, for the kernels that read them from a
+  // GoodFront (below)
+  PSG_DEV void begin_front(Grp<W>& g, const KArgs& a, uint64_t i, int32_t* crl) {
     id = instance_id(a, i);
     sc.setup(a, id, g.pid, g.valid);
     if (sc.crash_on) cs.prep(g, crl, sc.crash_round);
-    sc.prep_good(0, g.lane, a.R);
   }
   // Initial value of this lane's process: host-supplied, else seeded (0 for lanes past n)
   PSG_DEV int32_t x0(const Grp<W>& g, const KArgs& a, uint64_t i, int alg) const {
     if (!g.valid) return 0;
     return a.init ? init_x(a, i, id, g.pid) : sc.init_value(g.pid, alg);
+  }
+};
+
+// Good rounds of the seeded W == 1 kernels whose instances settle within a few rounds (OTR, OTR2:
+// the headline reads rounds 0..3 only). Sched::prep_good spends two wave-wide Philox passes per
+// instance on 64 rounds: call 0 of the round's PID_GLOBAL stream (word 0 the good flag, word 1
+// the first drop word) on every lane, call 1 (words 2, 3) on the lanes whose round is good. The
+// words are a pure function of (seed, instance, round, PID_GLOBAL, call), so here other lanes
+// draw the same words, call 0 on lanes 0..31 and call 1 on lanes 32..63 of one pass:
+//   front block: lane j + 8 r + 32 c draws call c of round r < 4 of batch row g0 + j, j < 8 — one
+//     pass per eight consecutive rows (a queue chunk, PSG_QUEUE_CHUNK_LANE), kept across instances;
+//   later rounds: lane l + 32 c draws call c of round base + l, l < 32 — one pass per 32 rounds of
+//     one instance, drawn when a round >= 4 first asks, into the registers of the front block:
+//     for the later rounds alone never more passes than prep_good's two per 64 rounds. The next
+//     row then draws a new front block, so an instance that runs past round 3 (0.1 % of the
+//     headline's) costs a front pass of its own, not an eighth of one: live through R = 40 that
+//     is 1 + 2 passes where prep_good drew 2, through R = 70 1 + 3 against 4.
+// The upper half hands its AND of words 2 and 3 (the drop words the launch has) to lane l - 32,
+// which forms flag and set exactly as prep_good does; drop words past call 1 (drop_log2 > 3) are
+// drawn on the good lanes on top. Rows of a front block past the batch are drawn and never read.
+struct GoodFront {
+  static constexpr int kRows = 8, kRounds = 4, kLate = 32;
+  static constexpr uint64_t kNone = 1ull << 63;
+  uint64_t g0 = kNone;  // uniform: first batch row of the front block held (kNone: none)
+  // lane j + 8 r: low word of the common HO set of round r of row g0 + j, lane j + 8 r + 32 its
+  // high word (later rounds: lanes l and l + 32, round base + l): one VGPR across the instances
+  uint32_t set;
+  uint32_t mask;        // uniform: bit j + 8 r (bit l) set iff that round is good
+  int base;             // uniform: first of the later rounds held in set / mask, in place of the front block
+
+  // One pass: lane l < 32 gets the good flag and the common set of round k of instance id, where
+  // lane l + 32 holds the same (id, k).
+  PSG_DEV static bool pass(const Sched<1, false>& sc, uint64_t id, uint32_t k, int lane, int R, uint64_t& s) {
+    const uint32_t c = (uint32_t)lane >> 5;
+    const U4 o = philox10((uint32_t)id, (uint32_t)(id >> 32), k, PID_GLOBAL + (c << 16), (uint32_t)sc.seed,
+                          (uint32_t)(sc.seed >> 32));
+    const uint64_t lo = (uint64_t)o.x | ((uint64_t)o.y << 32);
+    const uint64_t hi = (uint64_t)o.z | ((uint64_t)o.w << 32);
+    // call 1: words 2 and 3, as far as they are drop words; to lane l - 32
+    const uint64_t t = sc.drop >= 3 ? (lo & hi) : (sc.drop == 2 ? lo : ~0ull);
+    const uint64_t up = (uint64_t)xshfl<32>((uint32_t)t, lane) | ((uint64_t)xshfl<32>((uint32_t)(t >> 32), lane) << 32);
+    const bool good = lane < 32 && (int)k < R && o.x < sc.good_p32;
+    s = sc.full.w[0];
+    if (good && sc.drop > 0) {
+      uint64_t m = hi & up;  // words 1..3
+      for (uint32_t c2 = 2; 2 * c2 <= sc.drop; ++c2) {  // words 4..drop: call c2 holds words 2 c2, 2 c2 + 1
+        const U4 q = philox10((uint32_t)id, (uint32_t)(id >> 32), k, PID_GLOBAL + (c2 << 16), (uint32_t)sc.seed,
+                              (uint32_t)(sc.seed >> 32));
+        m &= (uint64_t)q.x | ((uint64_t)q.y << 32);
+        if (2 * c2 + 1 <= sc.drop) m &= (uint64_t)q.z | ((uint64_t)q.w << 32);
+      }
+      s &= ~m;
+      if (__builtin_popcountll(s) <= sc.good_min) s = sc.full.w[0];
+    }
+    return good;
+  }
+
+  // At the start of batch row i (uniform; sc set up for it): a new front block when the row is
+  // outside the one held. Rows come from the queue in increasing runs of a chunk. The lane's
+  // row and round are formed here per block (opaque copy), not hoisted out of the instance loop.
+  PSG_DEV void start(const Sched<1, false>& sc, const KArgs& a, uint64_t i, int lane) {
+    base = kRounds - kLate;
+    if (i - g0 < (uint64_t)kRows) return;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(lane));
+#endif
+    g0 = i;
+    uint64_t row = i + (uint64_t)(lane & (kRows - 1));
+    if (a.ids && row >= a.count) row = a.count - 1;  // the id list ends at a.count (i < a.count)
+    uint64_t s;
+    const bool good = pass(sc, instance_id(a, row), ((uint32_t)lane >> 3) & (uint32_t)(kRounds - 1), lane, a.R, s);
+    set = fold(s, lane);
+    mask = (uint32_t)__builtin_amdgcn_ballot_w64(good);
+  }
+  // the sets of lanes 0..31 as one word per lane: lane l keeps the low word, lane l + 32 takes the high one
+  PSG_DEV static uint32_t fold(uint64_t s, int lane) {
+    const uint32_t h = xshfl<32>((uint32_t)(s >> 32), lane);
+    return lane < 32 ? (uint32_t)s : h;
+  }
+  PSG_DEV uint64_t at(int off) const {
+    return (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)set, off) |
+           ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)set, off + 32) << 32);
+  }
+
+  // Sched::good_round for batch row i (uniform). The later rounds take the front block's place
+  // (they are asked for after rounds 0..3 of their instance), and the next row draws a new one.
+  PSG_DEV bool good_round(const Sched<1, false>& sc, uint64_t i, int k, int lane, int R, Mask<1>& s) {
+    if (sc.good_p32 == 0) return false;  // no good rounds in this launch (one scalar test per round)
+    int off = (int)(i - g0) + kRows * k;
+    if (k >= kRounds) {
+      if (k - base >= kLate) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+v"(lane));
+#endif
+        g0 = kNone;
+        base = k;
+        uint64_t ls;
+        const bool lg = pass(sc, sc.inst, (uint32_t)(k + (lane & (kLate - 1))), lane, R, ls);
+        set = fold(ls, lane);
+        mask = (uint32_t)__builtin_amdgcn_ballot_w64(lg);
+      }
+      off = k - base;
+    }
+    const bool good = (mask >> off) & 1u;
+    if (good) s.w[0] = at(off);
+    return good;
   }
 };
 

@@ -206,9 +206,13 @@ PSG_DEV void otr_check_initial(Grp<1>& g, Checks& ck, int n, int32_t x, uint32_t
 // Spec-program trace (a.trace == nullptr), known at compile time.
 // W == 1 takes its own forms of the per-instance setup and finish: X0Set::build_window,
 // otr_check_initial, and finish_instance_w1 with the WaveTally. W > 1 keeps the general forms.
+// The seeded, trace-free W == 1 forms with the built-in checker (kFront) read their good rounds
+// from a GoodFront (psg_device.hpp): rounds 0..3 of eight batch rows from one Philox pass, later
+// rounds 32 a pass. The traced and fused forms keep Sched::prep_good.
 template <int W, bool V2, bool XHO, class SH = NoHook, bool TR = true>
 PSG_DEV void otr_body(const KArgs& a) {
   const bool tracing_on = SH::kFused || (TR && a.trace != nullptr);
+  constexpr bool kFront = W == 1 && !XHO && !SH::kFused && !TR;
   __shared__ BlockCounters bc;
   __shared__ uint64_t xb[Grp<W>::kXb];
   __shared__ int32_t crl[W > 1 ? 64 * W : 1];
@@ -233,6 +237,7 @@ PSG_DEV void otr_body(const KArgs& a) {
   InstanceQueue<W, 0, W == 1 ? PSG_QUEUE_CHUNK_LANE : 0> Q;  // dynamic instance distribution (psg_device.hpp)
   StepTally tally;     // per-lane process-round steps, reduced once per wave
   WaveTally wtally;    // W == 1: the other counters' sums, flushed once per wave
+  GoodFront gf;        // kFront: the good rounds of the current eight batch rows
   // Host-supplied initial values are loaded one instance ahead: the next row's load is
   // issued when an instance starts and consumed when the next one does, so its latency
   // overlaps the current instance's rounds instead of stalling its setup.
@@ -249,7 +254,12 @@ PSG_DEV void otr_body(const KArgs& a) {
     x0next = load_x0(inext);
     pt.mark(4);
     Inst<W, XHO> in;
-    in.begin(g, a, i, crl);
+    if constexpr (kFront) {
+      in.begin_front(g, a, i, crl);
+      if (a.good_p32 != 0) gf.start(in.sc, a, i, g.lane);
+    } else {
+      in.begin(g, a, i, crl);
+    }
     Sched<W, XHO>& sc = in.sc;
     int32_t x0 = 0;
     if (g.valid) x0 = a.init ? x0host : sc.init_value(g.pid, PSG_ALG_OTR);
@@ -312,7 +322,9 @@ PSG_DEV void otr_body(const KArgs& a) {
         }
         if (!settled) {
         Mask<W> goodS;
-        const bool good = sc.good_round(k, g.lane, a.R, goodS);
+        bool good;
+        if constexpr (kFront) good = gf.good_round(sc, i, k, g.lane, a.R, goodS);
+        else good = sc.good_round(k, g.lane, a.R, goodS);
         pt.add(4, good ? 1u : 0u);  // event build: good rounds executed unsettled
         pt.add(5, good && !good_read ? 1u : 0u);  // ... the first of them in an instance
         if (PSG_PHASE_TIMERS == 2) good_read = good_read || good;
