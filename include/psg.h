@@ -452,6 +452,71 @@ int psg_population_next(psg_ctx* ctx, const uint32_t* parent, const uint8_t* op,
 /* Copy slots rows[0..k) of the loaded population to the host: ho [k][R][n][W], init [k][n] (nullable). */
 int psg_population_read(psg_ctx* ctx, const uint32_t* rows, size_t k, uint64_t* ho, int32_t* init);
 
+/* Population models: the crash-stop fault family and forced liveness rounds, on the device.
+ *
+ * Crash family (FloodMin / KSetAgreement / KSetEarlyStopping runners): the population is a genome
+ * crash [count][n] (crash round, -1 = correct) + partial [count][n][W] (receiver p's share of the
+ * crash-round messages) and the HO sets derived from it: q in HO(p, k) iff q is correct, or
+ * k < crash(q), or k == crash(q) and q in partial(p); then bits >= n are cleared and the self bit
+ * applied. Fresh genomes: f uniform in {0..fmax}, f distinct processes chosen uniformly, crash
+ * rounds uniform in {0..R-1}, partial bits independent at the instance's density. A mutant moves,
+ * adds (only while fewer than fmax are crashed) or removes at most one crash and toggles `flips`
+ * partial bits. Afterwards the context is as after psg_load_schedule(ho, crash): the checks that
+ * quantify over correct processes read the crash rounds.
+ *
+ * Liveness (omission family): after links, flips and repair, `live_rounds` rounds per instance are
+ * forced so that the algorithm's livenessPredicate holds in them, in every generation (a mutant
+ * cannot lose them; two drawn rounds may coincide):
+ *   good round        every HO(p, k) := one common set s, |s| > 2n/3 and |s| >= min_size (everyone
+ *                     with self_bit; else density ~0.9 topped up with random members)
+ *   coord hears all   HO(coord(k'), k') := everyone for every round k' of the phase (of `phase`
+ *                     rounds) containing the forced round, coord(k') = (k' / phase) % n
+ *   fixed coord       in the phase containing the forced round: slot 1, HO(coord) := everyone;
+ *                     slot 2, coord is added to every HO(p) */
+enum psg_pop_family { PSG_POP_OMISSION = 0, PSG_POP_CRASH = 1 };
+enum psg_pop_live {
+  PSG_LIVE_NONE = 0,
+  PSG_LIVE_GOOD_ROUND = 1,      /* example/Otr.scala:96-97 */
+  PSG_LIVE_COORD_HEARS_ALL = 2, /* example/LastVoting.scala:20-22, coord = (k / phase) % n */
+  PSG_LIVE_FIXED_COORD = 3      /* example/TwoPhaseCommit.scala:90-92 */
+};
+#define PSG_POP_MAX_LIVE 8
+typedef struct psg_population_model {
+  int32_t family;           /* enum psg_pop_family */
+  int32_t fmax;             /* crash: at most fmax crashed processes, 0..n */
+  uint32_t partial_p256[4]; /* crash: density/256 of the crash-round delivery sets; instance i uses level i % 4 */
+  uint32_t move_p256;       /* crash mutant: probabilities/256 of moving one crash round, ... */
+  uint32_t add_p256;        /* ... crashing one more process, ... */
+  uint32_t drop_p256;       /* ... un-crashing one: the three are summed into thresholds on one 8-bit draw, tried
+                               in this order, an impossible one falling through to the next (sum <= 256;
+                               the host search: 77, 77, 38) */
+  int32_t live_kind;        /* enum psg_pop_live; omission family only */
+  int32_t live_rounds;      /* 0..PSG_POP_MAX_LIVE rounds forced per instance */
+  int32_t live_at[PSG_POP_MAX_LIVE]; /* round of the j-th forced one; < 0: uniform in 0..R-1 per instance and
+                                        generation */
+  int32_t phase;            /* coordinator period (LastVoting / ShortLastVoting 4, TwoPhaseCommit 3) */
+  int32_t coord;            /* PSG_LIVE_FIXED_COORD: the coordinator */
+} psg_population_model;
+
+/* psg_population_fresh / _next under a model. PSG_POP_OMISSION with PSG_LIVE_NONE is exactly
+ * psg_population_fresh / _next. An invalid model (unknown family or kind, fmax outside 0..n, the
+ * crash family with min_size > 0 or a live kind, live_rounds outside 0..PSG_POP_MAX_LIVE,
+ * live_at[j] >= R, phase < 1, coord outside 0..n-1, move + add + drop > 256) is PSG_EINVAL and
+ * changes nothing. psg_population_next_model continues a population of the same family. */
+int psg_population_fresh_model(psg_ctx* ctx, uint64_t inst_begin, uint64_t count, const psg_population_params* p,
+                               const psg_population_model* m);
+int psg_population_next_model(psg_ctx* ctx, const uint32_t* parent, const uint8_t* op, const psg_population_params* p,
+                              const psg_population_model* m);
+/* The genome of slots rows[0..k) of a crash-family population: crash [k][n] int32 (-1 = correct)
+ * and partial [k][n][W] (nullable). */
+int psg_population_read_crash(psg_ctx* ctx, const uint32_t* rows, size_t k, int32_t* crash, uint64_t* partial);
+/* live [count][R] uint8: does the liveness predicate `live_kind` (enum psg_pop_live, not NONE) hold in
+ * round k of instance i of the loaded explicit schedule (a population, or psg_load_schedule's; count =
+ * its instance count)? Bits >= n of the sets are ignored. Good round: all n sets equal and larger than
+ * 2n/3; coord hears all: HO((k / phase) % n, k) is everyone; fixed coord: slot k % phase == 1, HO(coord)
+ * is everyone, slot 2, every HO(p) contains coord, other slots hold. */
+int psg_population_live(psg_ctx* ctx, int32_t live_kind, int32_t phase, int32_t coord, uint8_t* live);
+
 const char* psg_last_error(const psg_ctx* ctx);
 void psg_destroy(psg_ctx* ctx);
 

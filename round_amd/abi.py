@@ -232,3 +232,31 @@ class PopulationParams(C.Structure):
         ("value_range", C.c_int32),
         ("redraw_p256", C.c_uint32),
     ]
+
+
+# enum psg_pop_family / psg_pop_live
+PSG_POP_OMISSION, PSG_POP_CRASH = 0, 1
+PSG_LIVE_NONE, PSG_LIVE_GOOD_ROUND, PSG_LIVE_COORD_HEARS_ALL, PSG_LIVE_FIXED_COORD = 0, 1, 2, 3
+PSG_POP_MAX_LIVE = 8
+
+
+class PopulationModel(C.Structure):
+    """psg_population_model (include/psg.h): the fault family and the forced live rounds of a
+    device-side population. A new one is the plain omission family (phase 1, nothing forced)."""
+    _fields_ = [
+        ("family", C.c_int32),
+        ("fmax", C.c_int32),
+        ("partial_p256", C.c_uint32 * 4),
+        ("move_p256", C.c_uint32),
+        ("add_p256", C.c_uint32),
+        ("drop_p256", C.c_uint32),
+        ("live_kind", C.c_int32),
+        ("live_rounds", C.c_int32),
+        ("live_at", C.c_int32 * PSG_POP_MAX_LIVE),
+        ("phase", C.c_int32),
+        ("coord", C.c_int32),
+    ]
+
+    def __init__(self, *args, **kw):
+        kw.setdefault("phase", 1)
+        super().__init__(*args, **kw)

@@ -10,7 +10,10 @@ rounds of a progress step). Here the same assumptions constrain explicit HO
 schedules (round_amd/schedules.py) and the GPU executes and checks
 populations of them per launch (psg_load_schedule + psg_run_batch), so a
 search is a loop of: generate / mutate schedules on the host, run them all on
-the device, keep the ones that get closest to a violation.
+the device, keep the ones that get closest to a violation. (Device-resident
+populations, psg_population_*, generate and mutate on the GPU instead: the
+general-omission safety search always, the crash family and the liveness search
+with device_models=True.)
 
   * safety search: schedules satisfy the safety predicate on their HO sets;
     a violation of a target check slot is genuine only while the predicate
@@ -88,8 +91,9 @@ class Model:
     min_size: Optional[int] = None   # safety predicate |HO(p)| >= min_size (omission family)
     fmax: int = 0                    # crash family: at most fmax crashes
     predicate_slot: Optional[int] = None  # check slot recording the predicate on effective HO sets
-    liveness: Optional[str] = None   # "good_round" | "coord_hears_all"
+    liveness: Optional[str] = None   # "good_round" | "coord_hears_all" | "fixed_coord"
     phase: int = 4                   # coordinator period (coord = (r / phase) % n)
+    coord: int = 0                   # "fixed_coord": the coordinator of every phase
 
 
 def default_model(alg: psync.Algorithm, n: int) -> Model:
@@ -109,7 +113,7 @@ def default_model(alg: psync.Algorithm, n: int) -> Model:
     if a == abi.PSG_ALG_KSET_ES:
         return Model("crash", fmax=alg.param)
     if a == abi.PSG_ALG_TPC:
-        return Model("omission")  # (its livenessPredicate: schedules.fixed_coord_live; no liveness search)
+        return Model("omission", liveness="fixed_coord", phase=3, coord=alg.param)  # TwoPhaseCommit.scala:90-92
     if a == abi.PSG_ALG_LATTICE:
         return Model("omission")  # (TrivialSpec: no livenessPredicate to assume, no liveness search)
     raise ValueError(f"no fault model for {alg.class_name}")
@@ -167,7 +171,8 @@ class Adversary:
                  targets: Optional[Sequence[str]] = None, model: Optional[Model] = None,
                  population: int = 4096, values: int = 3, keep: float = 0.75, self_bit: bool = True,
                  live_rounds: int = 2, live_at: Optional[Sequence[int]] = None, seed: int = 1,
-                 evaluator: Optional[Callable] = None, device: int = 0, device_pop: bool = True):
+                 evaluator: Optional[Callable] = None, device: int = 0, device_pop: bool = True,
+                 device_models: bool = False):
         if mode not in ("safety", "liveness"):
             raise ValueError("mode must be 'safety' or 'liveness'")
         self.alg, self.n, self.R = alg, n, rounds
@@ -188,6 +193,7 @@ class Adversary:
         self.self_bit, self.live_rounds = self_bit, live_rounds
         self.live_at = None if live_at is None else list(live_at)
         self.device_pop = device_pop
+        self.device_models = device_models
         self.rng = np.random.default_rng(seed)
         self._own = evaluator is None
         self.evaluator = evaluator or GpuEvaluator(alg, n, rounds, population, device=device,
@@ -241,6 +247,11 @@ class Adversary:
                     ks = self.rng.integers(0, R, I)
                 if m.liveness == "good_round":
                     S.force_good_round(ho, self.rng, n, np.arange(I), ks, self_bit=self.self_bit)
+                elif m.liveness == "fixed_coord":
+                    for k in np.unique(ks):  # the whole phase: the coordinator hears all, then all hear it
+                        base = (int(k) // m.phase) * m.phase
+                        sel = np.nonzero(ks == k)[0]
+                        ho[sel] = S.force_fixed_coord(ho[sel], n, m.coord, range(base, min(R, base + m.phase)), m.phase)
                 else:
                     for i, k in enumerate(ks):
                         base = (k // m.phase) * m.phase  # a whole phase with the coordinator hearing all
@@ -254,6 +265,8 @@ class Adversary:
         m = self.model
         if m.liveness == "good_round":
             return S.good_round(ho, self.n).sum(1)
+        if m.liveness == "fixed_coord":
+            return S.fixed_coord_live(ho, self.n, m.coord).sum(1)
         return S.coord_hears_all(ho, self.n, m.phase).sum(1)
 
     def _mutate(self, g, strength):
@@ -317,9 +330,33 @@ class Adversary:
     # -------------------------------------------------------------- search
     def device_population(self) -> bool:
         """Can generations be generated and mutated on the GPU (psg_population_*)?
-        General omission, safety search, integer inputs, the GPU evaluator."""
-        return (self.model.family == "omission" and self.mode == "safety" and not self.alg.real
-                and isinstance(self.evaluator, GpuEvaluator) and self.device_pop)
+        General omission, safety search, integer inputs, the GPU evaluator; with
+        device_models also the crash family and the liveness search (psg_population_*_model)."""
+        ok = not self.alg.real and isinstance(self.evaluator, GpuEvaluator) and self.device_pop
+        if self.model.family == "omission" and self.mode == "safety":
+            return ok
+        return ok and self.device_models and self.live_rounds <= abi.PSG_POP_MAX_LIVE
+
+    def _pop_model(self):
+        """The psg_population_model of this search, or None for the plain omission family."""
+        m = self.model
+        if m.family == "omission" and self.mode == "safety":
+            return None
+        pm = abi.PopulationModel()
+        if m.family == "crash":
+            pm.family, pm.fmax = abi.PSG_POP_CRASH, m.fmax
+            for j, d in enumerate((0.05, 0.15, 0.5, 0.85)):  # the host generator's delivery densities
+                pm.partial_p256[j] = int(round(d * 256))
+            pm.move_p256, pm.add_p256, pm.drop_p256 = 77, 77, 38  # schedules.mutate_crash: 0.3, 0.3, 0.15
+            return pm
+        pm.family = abi.PSG_POP_OMISSION
+        pm.live_kind = {"good_round": abi.PSG_LIVE_GOOD_ROUND, "coord_hears_all": abi.PSG_LIVE_COORD_HEARS_ALL,
+                        "fixed_coord": abi.PSG_LIVE_FIXED_COORD}[m.liveness]
+        pm.live_rounds = self.live_rounds
+        for j in range(self.live_rounds):
+            pm.live_at[j] = -1 if self.live_at is None else self.live_at[j % len(self.live_at)]
+        pm.phase, pm.coord = m.phase, m.coord
+        return pm
 
     def _pop_params(self, generation):
         p = abi.PopulationParams()
@@ -327,7 +364,8 @@ class Adversary:
         if generation == 0:
             self._pop_seed = p.seed
         p.generation = generation
-        p.flips = max(1, int(self.n * self.R * 0.01))
+        # (crash family: one crash-round delivery toggled per mutant, as schedules.mutate_crash)
+        p.flips = 1 if self.model.family == "crash" else max(1, int(self.n * self.R * 0.01))
         p.min_size = self.model.min_size or 0
         p.self_bit = 1 if self.self_bit else 0
         for j, f in enumerate((0.7, 0.85, 1.0, 1.15)):  # the host generator's spread of loss rates
@@ -344,7 +382,11 @@ class Adversary:
         ctx = self.evaluator.gr._ctx
         base = self.next_id
         self.next_id += P
-        ctx.population_fresh(base, P, self._pop_params(0))
+        pm = self._pop_model()
+        if pm is None:
+            ctx.population_fresh(base, P, self._pop_params(0))
+        else:
+            ctx.population_fresh_model(base, P, self._pop_params(0), pm)
         found: List[Counterexample] = []
         t0 = time.perf_counter()
         gpu = 0.0
@@ -357,11 +399,18 @@ class Adversary:
             gpu += time.perf_counter() - t1
             ev = Eval(pi, dec, dr)
             bad, first = self._violations(ev)
+            if self.mode == "liveness":  # only instances with enough live rounds count (the host loop's `valid`)
+                t1 = time.perf_counter()
+                live = ctx.population_live(pm.live_kind, pm.phase, pm.coord)
+                gpu += time.perf_counter() - t1
+                bad &= live.sum(1) >= self.live_rounds
             rows = np.nonzero(bad)[0][:max(0, want - len(found))]
             if len(rows):
                 hos, inits = ctx.population_read(rows)
+                crashes = ctx.population_read_crash(rows)[0] if self.model.family == "crash" else None
                 for j, i in enumerate(rows):
-                    found.append(self._cex(base + int(i), inits[j], hos[j], None, pi[i], int(first[i])))
+                    found.append(self._cex(base + int(i), inits[j], hos[j], None if crashes is None else crashes[j],
+                                           pi[i], int(first[i])))
             score = self._score(ev)
             history.append(float(score.max()))
             if len(found) >= want or (time_budget is not None and time.perf_counter() - t0 > time_budget):
@@ -376,7 +425,10 @@ class Adversary:
             parent[:ne], op[:ne] = elite, 0
             parent[ne:ne + nm], op[ne:ne + nm] = elite[self.rng.integers(0, ne, nm)], 1
             t1 = time.perf_counter()
-            ctx.population_next(parent, op, self._pop_params(g))
+            if pm is None:
+                ctx.population_next(parent, op, self._pop_params(g))
+            else:
+                ctx.population_next_model(parent, op, self._pop_params(g), pm)
             gpu += time.perf_counter() - t1
         secs = time.perf_counter() - t0
         if shrink:

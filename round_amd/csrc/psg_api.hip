@@ -98,6 +98,11 @@ struct psg_buffers {
   DevBuf<int32_t> d_init2;
   DevBuf<uint32_t> d_parent;
   DevBuf<uint8_t> d_op;
+  // population models: the crash family's genome (crash rounds in d_crash, second buffer here;
+  // crash-round delivery sets [count][n][W], two generations) and psg_population_live's output
+  DevBuf<int32_t> d_crash2;
+  DevBuf<uint64_t> d_partial, d_partial2;
+  DevBuf<uint8_t> d_live;
   DevBuf<int32_t> d_dec;
   DevBuf<uint8_t> d_dround;
   DevBuf<psg_instance_summary> d_inst;
@@ -126,6 +131,7 @@ struct psg_ctx : psg_buffers {
   uint64_t staged_begin = 0, staged_count = 0;
   // explicit schedule (psg_load_schedule)
   bool ho_loaded = false, ho_has_crash = false;
+  bool pop_crash = false;  // the loaded schedule is a crash-family population (its genome is on the device)
   uint64_t ho_begin = 0, ho_count = 0;
   uint64_t last_count = 0;
   int grid_max = 0;  // resident blocks for the algorithm's kernel
@@ -1279,6 +1285,7 @@ int psg_load_schedule(psg_ctx* c, uint64_t inst_begin, uint64_t count, const uin
   }
   c->ho_loaded = true;
   c->ho_has_crash = crash_round != nullptr;
+  c->pop_crash = false;
   c->ho_begin = inst_begin;
   c->ho_count = count;
   return PSG_OK;
@@ -1289,6 +1296,7 @@ int psg_clear_schedule(psg_ctx* c) {
   for (psg_ctx* s : c->subs) (void)psg_clear_schedule(s);
   c->ho_loaded = false;
   c->ho_has_crash = false;
+  c->pop_crash = false;
   c->ho_begin = c->ho_count = 0;
   return PSG_OK;
 }
@@ -1381,32 +1389,95 @@ static PopArgs pop_args(const psg_ctx* c, const psg_population_params* p, uint64
   return a;
 }
 
-int psg_population_fresh(psg_ctx* c, uint64_t inst_begin, uint64_t count, const psg_population_params* p) {
+// Room for the crash family's genome of `count` instances, both generations (d_crash itself:
+// sched_buffers).
+static int pop_crash_buffers(psg_ctx* c, uint64_t count) {
+  const uint64_t cells = count * (uint64_t)c->cfg.n;
+  HIPCHK(c, c->d_crash2.grow(cells));
+  HIPCHK(c, c->d_partial.grow(cells * (uint64_t)c->W));
+  HIPCHK(c, c->d_partial2.grow(cells * (uint64_t)c->W));
+  return PSG_OK;
+}
+
+static bool live_kind_known(int32_t k) { return k >= PSG_LIVE_NONE && k <= PSG_LIVE_FIXED_COORD; }
+
+// null model: the plain omission family (psg_population_fresh / _next)
+static int model_check(psg_ctx* c, const psg_population_params* p, const psg_population_model* m) {
+  if (!m) return PSG_OK;
+  const int n = c->cfg.n;
+  if (m->family != PSG_POP_OMISSION && m->family != PSG_POP_CRASH) return fail(c, PSG_EINVAL, "unknown population family");
+  if (!live_kind_known(m->live_kind)) return fail(c, PSG_EINVAL, "unknown liveness kind");
+  if (m->fmax < 0 || m->fmax > n) return fail(c, PSG_EINVAL, "fmax outside 0..n");
+  if (m->family == PSG_POP_CRASH && (p->min_size > 0 || m->live_kind != PSG_LIVE_NONE))
+    return fail(c, PSG_EINVAL, "the crash family takes neither min_size nor a liveness kind");
+  if ((uint64_t)m->move_p256 + m->add_p256 + m->drop_p256 > 256u)
+    return fail(c, PSG_EINVAL, "move_p256 + add_p256 + drop_p256 > 256");
+  if (m->live_rounds < 0 || m->live_rounds > PSG_POP_MAX_LIVE) return fail(c, PSG_EINVAL, "live_rounds outside 0..PSG_POP_MAX_LIVE");
+  for (int j = 0; j < m->live_rounds; ++j)
+    if (m->live_at[j] >= c->cfg.rounds) return fail(c, PSG_EINVAL, "live_at beyond the last round");
+  if (m->phase < 1) return fail(c, PSG_EINVAL, "phase must be >= 1");
+  if (m->coord < 0 || m->coord >= n) return fail(c, PSG_EINVAL, "coord outside 0..n-1");
+  return PSG_OK;
+}
+
+static void pop_model_args(PopArgs& a, const psg_population_model* m) {
+  if (!m) return;
+  a.fmax = m->fmax;
+  for (int j = 0; j < 4; ++j) a.partial_p[j] = m->partial_p256[j];
+  a.t_move = m->move_p256;
+  a.t_add = a.t_move + m->add_p256;
+  a.t_drop = a.t_add + m->drop_p256;
+  a.live_kind = m->live_kind;
+  a.live_rounds = m->live_rounds;
+  for (int j = 0; j < PSG_POP_MAX_LIVE; ++j) a.live_at[j] = m->live_at[j];
+  a.phase = m->phase;
+  a.coord = m->coord;
+}
+
+static int population_fresh(psg_ctx* c, uint64_t inst_begin, uint64_t count, const psg_population_params* p,
+                            const psg_population_model* m) {
   if (!c) return PSG_EINVAL;
   if (!c->subs.empty()) return fail(c, PSG_EINVAL, "device-resident populations need a single-device context");
   if (int rc = pop_check(c, p)) return rc;
+  if (int rc = model_check(c, p, m)) return rc;
   if (count > c->cap) return fail(c, PSG_ERANGE, "inst_count exceeds batch_capacity");
+  const bool crash = m && m->family == PSG_POP_CRASH;
   HIPCHK(c, hipSetDevice(c->cfg.device));
   if (int rc = pop_buffers(c, std::max<uint64_t>(count, 1))) return rc;
+  if (crash)
+    if (int rc = pop_crash_buffers(c, std::max<uint64_t>(count, 1))) return rc;
   PopArgs a = pop_args(c, p, count);
+  pop_model_args(a, m);
   a.ho = c->d_ho;
   a.init = c->d_init;
-  HIPCHK(c, launch_population(a, c->stream));
+  if (crash) {
+    a.crash = c->d_crash;
+    a.partial = c->d_partial;
+    HIPCHK(c, launch_population_crash(a, c->stream));
+  } else {
+    HIPCHK(c, launch_population(a, c->stream));
+    HIPCHK(c, launch_population_live(a, c->stream));
+  }
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->ho_loaded = true;
-  c->ho_has_crash = false;
+  c->ho_has_crash = crash;
+  c->pop_crash = crash;
   c->ho_begin = inst_begin;
   c->ho_count = count;
   set_staged(c, inst_begin, count, false);
   return PSG_OK;
 }
 
-int psg_population_next(psg_ctx* c, const uint32_t* parent, const uint8_t* op, const psg_population_params* p) {
+static int population_next(psg_ctx* c, const uint32_t* parent, const uint8_t* op, const psg_population_params* p,
+                           const psg_population_model* m) {
   if (!c) return PSG_EINVAL;
   if (!c->subs.empty()) return fail(c, PSG_EINVAL, "device-resident populations need a single-device context");
   if (int rc = pop_check(c, p)) return rc;
+  if (int rc = model_check(c, p, m)) return rc;
   if (!(c->ho_loaded && is_staged(c, c->ho_begin, c->ho_count)) || pop_capacity(c) < c->ho_count)
     return fail(c, PSG_EINVAL, "no population loaded (psg_population_fresh first)");
+  const bool crash = m && m->family == PSG_POP_CRASH;
+  if (crash != c->pop_crash) return fail(c, PSG_EINVAL, "the loaded population is of the other fault family");
   const uint64_t count = c->ho_count;
   if (count && (!parent || !op)) return fail(c, PSG_EINVAL, "null parent / op");
   for (uint64_t i = 0; i < count; ++i) {
@@ -1417,16 +1488,97 @@ int psg_population_next(psg_ctx* c, const uint32_t* parent, const uint8_t* op, c
   HIPCHK(c, hipMemcpyAsync(c->d_parent, parent, sizeof(uint32_t) * count, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->d_op, op, count, hipMemcpyHostToDevice, c->stream));
   PopArgs a = pop_args(c, p, count);
+  pop_model_args(a, m);
   a.src = c->d_ho;
   a.ho = c->d_ho2;
   a.src_init = c->d_init;
   a.init = c->d_init2;
   a.parent = c->d_parent;
   a.op = c->d_op;
-  HIPCHK(c, launch_population(a, c->stream));
+  if (crash) {
+    a.src_crash = c->d_crash;
+    a.crash = c->d_crash2;
+    a.src_partial = c->d_partial;
+    a.partial = c->d_partial2;
+    HIPCHK(c, launch_population_crash(a, c->stream));
+  } else {
+    HIPCHK(c, launch_population(a, c->stream));
+    HIPCHK(c, launch_population_live(a, c->stream));
+  }
   HIPCHK(c, hipStreamSynchronize(c->stream));
   std::swap(c->d_ho, c->d_ho2);  // the new generation is the loaded schedule / staged inputs; the
   std::swap(c->d_init, c->d_init2);  // capacities go with the buffers
+  if (crash) {
+    std::swap(c->d_crash, c->d_crash2);
+    std::swap(c->d_partial, c->d_partial2);
+  }
+  return PSG_OK;
+}
+
+int psg_population_fresh(psg_ctx* c, uint64_t inst_begin, uint64_t count, const psg_population_params* p) {
+  return population_fresh(c, inst_begin, count, p, nullptr);
+}
+
+int psg_population_next(psg_ctx* c, const uint32_t* parent, const uint8_t* op, const psg_population_params* p) {
+  return population_next(c, parent, op, p, nullptr);
+}
+
+int psg_population_fresh_model(psg_ctx* c, uint64_t inst_begin, uint64_t count, const psg_population_params* p,
+                               const psg_population_model* m) {
+  if (!c) return PSG_EINVAL;
+  if (!m) return fail(c, PSG_EINVAL, "null population model");
+  return population_fresh(c, inst_begin, count, p, m);
+}
+
+int psg_population_next_model(psg_ctx* c, const uint32_t* parent, const uint8_t* op, const psg_population_params* p,
+                              const psg_population_model* m) {
+  if (!c) return PSG_EINVAL;
+  if (!m) return fail(c, PSG_EINVAL, "null population model");
+  return population_next(c, parent, op, p, m);
+}
+
+int psg_population_read_crash(psg_ctx* c, const uint32_t* rows, size_t k, int32_t* crash, uint64_t* partial) {
+  if (!c || (!rows && k) || (!crash && k)) return PSG_EINVAL;
+  if (!c->subs.empty()) return fail(c, PSG_EINVAL, "device-resident populations need a single-device context");
+  if (!c->ho_loaded || !c->pop_crash) return fail(c, PSG_EINVAL, "no crash-family population loaded");
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  const uint64_t n = (uint64_t)c->cfg.n, W = (uint64_t)c->W;
+  for (size_t j = 0; j < k; ++j) {
+    if (rows[j] >= c->ho_count) return fail(c, PSG_ERANGE, "row outside the population");
+    HIPCHK(c, hipMemcpy(crash + j * n, c->d_crash + (uint64_t)rows[j] * n, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+    if (partial)
+      HIPCHK(c, hipMemcpy(partial + j * n * W, c->d_partial + (uint64_t)rows[j] * n * W, sizeof(uint64_t) * n * W,
+                          hipMemcpyDeviceToHost));
+  }
+  return PSG_OK;
+}
+
+int psg_population_live(psg_ctx* c, int32_t live_kind, int32_t phase, int32_t coord, uint8_t* live) {
+  if (!c) return PSG_EINVAL;
+  if (!c->subs.empty()) return fail(c, PSG_EINVAL, "device-resident populations need a single-device context");
+  if (c->cfg.alg == PSG_ALG_EPSILON) return fail(c, PSG_EINVAL, "populations hold int32 inputs (not EpsilonConsensus)");
+  if (!c->ho_loaded) return fail(c, PSG_EINVAL, "no explicit schedule loaded");
+  if (!live_kind_known(live_kind) || live_kind == PSG_LIVE_NONE) return fail(c, PSG_EINVAL, "unknown liveness kind");
+  if (phase < 1) return fail(c, PSG_EINVAL, "phase must be >= 1");
+  if (coord < 0 || coord >= c->cfg.n) return fail(c, PSG_EINVAL, "coord outside 0..n-1");
+  const uint64_t cells = c->ho_count * (uint64_t)c->cfg.rounds;
+  if (cells == 0) return PSG_OK;
+  if (!live) return fail(c, PSG_EINVAL, "null output");
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  HIPCHK(c, c->d_live.grow(cells));
+  LiveArgs a;
+  a.ho = c->d_ho;
+  a.live = c->d_live;
+  a.count = c->ho_count;
+  a.n = c->cfg.n;
+  a.R = c->cfg.rounds;
+  a.W = c->W;
+  a.kind = live_kind;
+  a.phase = phase;
+  a.coord = coord;
+  HIPCHK(c, launch_live_predicate(a, c->stream));
+  HIPCHK(c, hipMemcpyAsync(live, c->d_live, cells, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   return PSG_OK;
 }
 

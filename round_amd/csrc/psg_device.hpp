@@ -122,6 +122,24 @@ struct PopArgs {
   int32_t V;
   uint32_t redraw;
   int init_kind;  // POP_INIT_*
+  // population models (psg_population_model): the crash-family genome and the forced live rounds
+  int32_t* crash;               // destination crash rounds [count][n]
+  const int32_t* src_crash;     // current crash rounds
+  uint64_t* partial;            // destination crash-round delivery sets [count][n][W]
+  const uint64_t* src_partial;  // current ones
+  int32_t fmax;
+  uint32_t partial_p[4];
+  uint32_t t_move, t_add, t_drop;  // cumulative thresholds on the mutant's 8-bit draw
+  int32_t live_kind, live_rounds, phase, coord;
+  int32_t live_at[PSG_POP_MAX_LIVE];
+};
+// psg_population_live's kernel: live [count][R] over the sets ho [count][R][n][W]
+struct LiveArgs {
+  const uint64_t* ho;
+  uint8_t* live;
+  uint64_t count;
+  int n, R, W;
+  int32_t kind, phase, coord;
 };
 // a population's initial values: {1..V}; BenOr's {0, 1} coin bit; TwoPhaseCommit's vote (tpc_vote);
 // LatticeAgreement's set (lattice_init)

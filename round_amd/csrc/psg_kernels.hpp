@@ -9,6 +9,7 @@ namespace psg {
 struct KArgs;
 struct VmArgs;
 struct PopArgs;
+struct LiveArgs;
 
 // Runtime W (mask words, 1..4) -> compile-time constant: f(std::integral_constant<int, W>) for a
 // generic callable f, `bad` outside that range.
@@ -52,6 +53,11 @@ const void* lattice_kernel_ptr(int W);
 hipError_t launch_champ_selftest(const uint64_t* sets, int count, int tiebreak, int32_t* out, hipStream_t s);
 hipError_t launch_schedule(const KArgs& a, int W, int grid, uint64_t* ho_out, int32_t* crash_out, hipStream_t s);
 hipError_t launch_population(const PopArgs& a, hipStream_t s);
+// population models: the forced live rounds over a.ho (after launch_population), a crash-family
+// generation (genome, its HO sets, initial values), the liveness predicate per (instance, round)
+hipError_t launch_population_live(const PopArgs& a, hipStream_t s);
+hipError_t launch_population_crash(const PopArgs& a, hipStream_t s);
+hipError_t launch_live_predicate(const LiveArgs& a, hipStream_t s);
 hipError_t launch_spec_vm(const VmArgs& a, int grid, hipStream_t s);
 hipError_t launch_gen_init(uint64_t inst_begin, uint64_t count, int n, int alg, int V, uint64_t seed, int32_t* out,
                            hipStream_t s);

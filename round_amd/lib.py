@@ -25,7 +25,9 @@ EXPORTED_SYMBOLS = [
     "psg_fetch_instances", "psg_last_error", "psg_destroy", "psg_create_error",
     "psg_selftest_map_head", "psg_load_inputs_f64", "psg_copy_decisions_f64", "psg_fetch_instances_f64",
     "psg_run_batch_spec", "psg_load_schedule", "psg_clear_schedule", "psg_materialize_schedule",
-    "psg_population_fresh", "psg_population_next", "psg_population_read", "psg_spec_from_text", "psg_spec_release",
+    "psg_population_fresh", "psg_population_next", "psg_population_read", "psg_population_fresh_model",
+    "psg_population_next_model", "psg_population_read_crash", "psg_population_live", "psg_spec_from_text",
+    "psg_spec_release",
     "psg_spec_compile_native", "psg_spec_native_source", "psg_selftest_bitset", "psg_spec_rewrite_text",
     "psg_spec_set_options", "psg_pack_width",
 ]
@@ -79,6 +81,12 @@ def load():
     L.psg_population_fresh.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(abi.PopulationParams)]
     L.psg_population_next.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(abi.PopulationParams)]
     L.psg_population_read.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    L.psg_population_fresh_model.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(abi.PopulationParams),
+                                             C.POINTER(abi.PopulationModel)]
+    L.psg_population_next_model.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(abi.PopulationParams),
+                                            C.POINTER(abi.PopulationModel)]
+    L.psg_population_read_crash.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    L.psg_population_live.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
     L.psg_spec_from_text.argtypes = [C.c_char_p, C.c_int32, C.POINTER(abi.SpecProgram), C.c_char_p, C.c_size_t,
                                      C.c_char_p, C.c_size_t]
     try:  # (A/B builds of older kernels, PSG_LIB, may predate these; test_abi checks the in-tree library)
@@ -259,9 +267,11 @@ class Context:
                 raise ValueError("crash must be [count][n] int32")
         self._check(load().psg_load_schedule(self._h, inst_begin, count, ho.ctypes.data_as(C.c_void_p),
                                              None if cr is None else cr.ctypes.data_as(C.c_void_p)))
+        self._ho_count = count
 
     def clear_schedule(self):
         self._check(load().psg_clear_schedule(self._h))
+        self._ho_count = 0
 
     def materialize_schedule(self, inst_begin, count):
         """The seeded schedule: (ho uint64 [count][R][n][W], crash int32 [count][n])."""
@@ -276,6 +286,7 @@ class Context:
     def population_fresh(self, inst_begin, count, params):
         """psg_population_fresh: a random population of explicit schedules + inputs, on the device."""
         self._check(load().psg_population_fresh(self._h, inst_begin, count, C.byref(params)))
+        self._ho_count = count
 
     def population_next(self, parent, op, params):
         """psg_population_next: slot i <- copy (op 0) / mutant (1) of slot parent[i], or fresh (2)."""
@@ -298,6 +309,45 @@ class Context:
         self._check(load().psg_population_read(self._h, rows.ctypes.data_as(C.c_void_p), k,
                                                ho.ctypes.data_as(C.c_void_p), init.ctypes.data_as(C.c_void_p)))
         return ho, init
+
+    def population_fresh_model(self, inst_begin, count, params, model):
+        """psg_population_fresh_model: population_fresh under a fault family / forced live rounds
+        (abi.PopulationModel)."""
+        self._check(load().psg_population_fresh_model(self._h, inst_begin, count, C.byref(params), C.byref(model)))
+        self._ho_count = count
+
+    def population_next_model(self, parent, op, params, model):
+        """psg_population_next_model: population_next under the model of the loaded population."""
+        import numpy as np
+        parent = np.ascontiguousarray(parent, np.uint32)
+        op = np.ascontiguousarray(op, np.uint8)
+        if parent.shape != op.shape:
+            raise ValueError("parent and op must have one entry per slot")
+        self._check(load().psg_population_next_model(self._h, parent.ctypes.data_as(C.c_void_p),
+                                                     op.ctypes.data_as(C.c_void_p), C.byref(params), C.byref(model)))
+
+    def population_read_crash(self, rows):
+        """Genome of slots `rows` of a crash-family population: (crash int32 [k][n], -1 = correct;
+        partial uint64 [k][n][W])."""
+        import numpy as np
+        rows = np.ascontiguousarray(rows, np.uint32)
+        k = int(rows.shape[0])
+        W = (self.cfg.n + 63) // 64
+        crash = np.zeros((k, self.cfg.n), np.int32)
+        partial = np.zeros((k, self.cfg.n, W), np.uint64)
+        self._check(load().psg_population_read_crash(self._h, rows.ctypes.data_as(C.c_void_p), k,
+                                                     crash.ctypes.data_as(C.c_void_p),
+                                                     partial.ctypes.data_as(C.c_void_p)))
+        return crash, partial
+
+    def population_live(self, live_kind, phase=1, coord=0):
+        """psg_population_live: uint8 [count][R], the liveness predicate (abi.PSG_LIVE_*) per
+        (instance, round) of the explicit schedule this context loaded (load_schedule or a
+        population; count = its instances)."""
+        import numpy as np
+        live = np.zeros((getattr(self, "_ho_count", 0), self.cfg.rounds), np.uint8)
+        self._check(load().psg_population_live(self._h, live_kind, phase, coord, live.ctypes.data_as(C.c_void_p)))
+        return live
 
     def close(self):
         if getattr(self, "_h", None):

@@ -245,6 +245,19 @@ def force_coord_hears_all(ho: np.ndarray, n: int, rounds=None, phase: int = 4) -
     return ho
 
 
+def force_fixed_coord(ho: np.ndarray, n: int, coord: int, rounds=None, phase: int = 3) -> np.ndarray:
+    """TwoPhaseCommit's livenessPredicate in the given rounds (all by default): in slot 1 of a
+    phase HO(coord) := all processes, in slot 2 coord joins every HO(p) (fixed_coord_live)."""
+    fm = full_mask(n)
+    R = ho.shape[1]
+    for k in (range(R) if rounds is None else rounds):
+        if k % phase == 1:
+            ho[:, k, coord, :] = fm
+        elif k % phase == 2:
+            ho[:, k, :, coord >> 6] |= np.uint64(1 << (coord & 63))
+    return ho
+
+
 def flip_links(ho: np.ndarray, rng, n: int, per_instance: int, self_bit: bool = True) -> np.ndarray:
     """Flip `per_instance` random links (k, p, q) of every instance (q != p when self_bit)."""
     I, R = ho.shape[:2]

@@ -7,7 +7,13 @@ Rows (one JSON line each, then a JSON list in --out):
   * reference OTR n=64 R=20, safety search, 2^15 schedules per generation: no
     counterexample expected; reports schedules/s and the GPU share of the time;
   * mutants (OTR, LastVoting, FloodMin, BenOr): generations / seconds / schedules
-    to the first counterexample and the shrunk counterexample's size.
+    to the first counterexample and the shrunk counterexample's size;
+  * reference FloodMin(f=3) n=64 R=6 (crash-stop family) and OTR liveness n=64 R=20 with good
+    rounds 0 and 1, 2^15 schedules per generation, no counterexample expected: the two search
+    shapes whose generations stay on the host unless --device-models moves them to the GPU
+    (psg_population_*_model).
+--ab-models N measures those two rows only: one warm-up search per row and path, then N passes
+alternating the host-generator and the device-model path.
 """
 import argparse
 import json
@@ -21,11 +27,15 @@ sys.path.insert(0, ROOT)
 from round_amd import adversary as A, psync  # noqa: E402
 
 
-def row(name, alg, n, R, targets=None, population=4096, generations=10, want=1, stop=True, values=3):
+def row(name, alg, n, R, targets=None, population=4096, generations=10, want=1, stop=True, values=3,
+        device_models=False, **search_kw):
     t0 = time.perf_counter()
-    with A.Adversary(alg, n, R, targets=targets, population=population, values=values, seed=7) as adv:
+    with A.Adversary(alg, n, R, targets=targets, population=population, values=values, seed=7,
+                     device_models=device_models, **search_kw) as adv:
+        device = adv.device_population()
         res = adv.search(generations=generations, want=want if stop else 10 ** 9, shrink=stop)
     out = {"row": name, "class": alg.class_name, "variant": alg.variant, "n": n, "rounds": R,
+           "device_population": device, "gpu_share": round(res.gpu_seconds / res.seconds, 3) if res.seconds else 0.0,
            "population": population, "generations": res.generations,
            "schedules": res.schedules_evaluated, "seconds": round(res.seconds, 3),
            "schedules_per_s": round(res.schedules_per_second, 1),
@@ -39,12 +49,38 @@ def row(name, alg, n, R, targets=None, population=4096, generations=10, want=1, 
     return out
 
 
+def model_rows(population, generations, device_models, **extra):
+    """The crash-stop and the liveness reference rows (host generator unless device_models)."""
+    out = [row("ref_floodmin_n64", psync.FloodMin(3), 64, 6, population=population, generations=generations,
+               stop=False, device_models=device_models),
+           row("live_otr_n64", psync.OTR(), 64, 20, population=population, generations=generations, stop=False,
+               device_models=device_models, mode="liveness", live_at=[0, 1])]
+    for r in out:
+        r.update(extra)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--device-models", action="store_true",
+                    help="crash-stop and liveness searches generate their populations on the GPU")
+    ap.add_argument("--ab-models", type=int, default=0, metavar="N",
+                    help="only the two model rows: a warm-up, then N passes alternating host and device generation")
     ap.add_argument("--out", default="")
     ap.add_argument("--population", type=int, default=32768)
     ap.add_argument("--generations", type=int, default=8)
     a = ap.parse_args()
+    if a.ab_models:
+        rows = []
+        for dm in (False, True):
+            model_rows(a.population, 2, dm, warmup=True)
+        for k in range(a.ab_models):
+            for dm in (False, True):
+                rows += model_rows(a.population, a.generations, dm, **{"pass": k})
+        if a.out:
+            with open(a.out, "w") as f:
+                json.dump(rows, f, indent=1)
+        return
     rows = [row("ref_otr_n64", psync.OTR(), 64, 20, population=a.population, generations=a.generations,
                 stop=False, values=3)]
     rows.append(row("mut_otr_n64_safety", psync.OTR(variant=1), 64, 8, ["Safety"], population=4096, generations=60))
@@ -52,8 +88,10 @@ def main():
                     generations=60, values=2))
     rows.append(row("mut_lv_n8_agreement", psync.LastVoting(variant=1), 8, 12, ["Agreement"], population=4096,
                     generations=60))
-    rows.append(row("mut_floodmin_n8", psync.FloodMin(2, variant=1), 8, 4, population=4096, generations=60))
+    rows.append(row("mut_floodmin_n8", psync.FloodMin(2, variant=1), 8, 4, population=4096, generations=60,
+                    device_models=a.device_models))
     rows.append(row("mut_benor_n8", psync.BenOr(variant=1), 8, 12, population=4096, generations=60, values=2))
+    rows += model_rows(a.population, a.generations, a.device_models)
     if a.out:
         with open(a.out, "w") as f:
             json.dump(rows, f, indent=1)
