@@ -178,6 +178,8 @@ struct AlgRow {
   const char* (*invalid)(const psg_config& cfg);     // the parameter rule the config breaks, or null
   hipError_t (*launch)(const KArgs& a, int W, int grid, hipStream_t s);
   const void* (*kernel)(int W);                      // the variant the resident-block count is taken from
+  // nullable: the variant a plain schedule (plain_schedule) is launched with, where the launcher has one
+  const void* (*kernel_plain)(int W) = nullptr;
 };
 
 static const char* need_value_range(const psg_config& c) { return c.value_range < 1 ? "value_range must be >= 1" : nullptr; }
@@ -206,7 +208,7 @@ static const char* otr_invalid(const psg_config& c) {
 static const AlgRow k_algs[] = {
     {},  // (PSG_ALG_* start at 1)
     {"example.OTR", k_names_otr, [](psg_config& c, int) { c.param = 2; /* afterDecision (Otr.scala:89) */ }, otr_invalid,
-     launch_otr, otr_kernel_ptr},
+     launch_otr, otr_kernel_ptr, otr_plain_kernel_ptr},
     {"example.LastVoting", k_names_lv, lv_defaults, need_value_range, launch_lv, lv_kernel_ptr},
     {"example.FloodMin", k_names_k, [](psg_config& c, int) { crash_stop_defaults(c, 4, 2); },
      [](const psg_config& c) {
@@ -230,7 +232,7 @@ static const AlgRow k_algs[] = {
      },
      [](const psg_config&) -> const char* { return nullptr; }, launch_benor, benor_kernel_ptr},
     {"example.OTR2", k_names_otr, [](psg_config& c, int) { c.param = 2; /* afterDecision (Otr2.scala:69) */ }, otr_invalid,
-     launch_otr2, otr2_kernel_ptr},
+     launch_otr2, otr2_kernel_ptr, otr2_plain_kernel_ptr},
     {"example.ShortLastVoting", k_names_k,
      [](psg_config& c, int n) {
        lv_defaults(c, n);
@@ -714,8 +716,12 @@ int psg_create(psg_ctx** out, const psg_config* cfg) {
   CK(c->d_counters.grow(NCOUNTERS_ALLOC));
   if (cfg->alg == PSG_ALG_KSET && c->W > 1)  // 520 + 4n bytes per batch row (psg_kset.hip hand-off)
     CK(c->d_hand.grow(65 * c->cap + (cells + 1) / 2));  // (the int32 decisions: two to a word)
+  // the grid is sized from the kernel this context's seeded launches go to (the schedule is fixed here)
+  const AlgRow* row = alg_row(cfg->alg);
+  const bool plain = row->kernel_plain && plain_schedule(make_args(c));
   int per_cu = 0;
-  CK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, alg_row(cfg->alg)->kernel(c->W), threads_per_block(c->W), 0));
+  CK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, plain ? row->kernel_plain(c->W) : row->kernel(c->W),
+                                                  threads_per_block(c->W), 0));
   hipDeviceProp_t prop;
   CK(hipGetDeviceProperties(&prop, cfg->device));
   if (per_cu < 1) per_cu = 1;

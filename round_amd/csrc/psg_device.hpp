@@ -76,6 +76,14 @@ struct KArgs {
   int32_t* hand_dec;
 };
 
+// A plain seeded schedule: no crashes and no ho_min (HOSchedule's defaults). The launchers that
+// have a kernel for it (OTR, OTR2 at W == 1) choose it by this test.
+// (-DPSG_PLAIN_SCHEDULE=0: an A/B build that sends every launch to the general kernels)
+#ifndef PSG_PLAIN_SCHEDULE
+#define PSG_PLAIN_SCHEDULE 1
+#endif
+inline bool plain_schedule(const KArgs& a) { return PSG_PLAIN_SCHEDULE && a.crash_fmax < 0 && a.ho_min < 0; }
+
 // Global instance id of batch element i: the explicit id list, else consecutive ids.
 PSG_DEV uint64_t instance_id(const KArgs& a, uint64_t i) { return a.ids ? a.ids[i] : a.inst_begin + i; }
 // Initial value of process pid of batch element i (global id inst): staged rows
@@ -161,7 +169,7 @@ enum { C_FAIL = 0, C_DECIDED = PSG_MAX_CHECKS, C_DIGEST = PSG_MAX_CHECKS + 1,
        // instance queues (InstanceQueue): NQUEUES counters, one per 128 B line
        // (two regions: a launch's second kernel — packed KSet's uniform-t tail — takes its own)
        C_QUEUE = NCOUNTERS, NQUEUES = 8, QUEUE_STRIDE = 16, NQUEUE_REGIONS = 2,
-       C_TIMER = C_QUEUE + NQUEUE_REGIONS * NQUEUES * QUEUE_STRIDE, NTIMERS = 8, NSTAMP_WAVES = 16384,
+       C_TIMER = C_QUEUE + NQUEUE_REGIONS * NQUEUES * QUEUE_STRIDE, NTIMERS = 12, NSTAMP_WAVES = 16384,
        T_RT_SUM = NTIMERS, T_RT_MIN = NTIMERS + 1, T_RT_MAX = NTIMERS + 2, T_WAVES = NTIMERS + 3,
        T_STAMPS = NTIMERS + 4,
        NTIMER_SLOTS = PSG_PHASE_TIMERS ? T_STAMPS + 2 * NSTAMP_WAVES : 0, NCOUNTERS_ALLOC = C_TIMER + NTIMER_SLOTS };
@@ -274,6 +282,38 @@ PSG_DEV U4 philox10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t
     k1 += 0xBB67AE85u;
   }
   return U4{c0, c1, c2, c3};
+}
+
+// Two calls that differ in counter word 3 alone (two calls of one word stream), round by round
+// side by side: oa = philox10(c0, c1, c2, c3a, k0, k1), ob = philox10(c0, c1, c2, c3b, k0, k1).
+// One call is a single dependent chain of multiplies; two give every product an independent
+// neighbour in the other chain, and share the round keys and whatever the calls have in common.
+PSG_DEV void philox10_pair(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3a, uint32_t c3b, uint32_t k0, uint32_t k1,
+                           U4& oa, U4& ob) {
+  uint32_t a0 = c0, a1 = c1, a2 = c2, a3 = c3a, b0 = c0, b1 = c1, b2 = c2, b3 = c3b;
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint64_t pa0 = PSG_MUL64(r, 0xD2511F53u, a0);
+    const uint64_t pb0 = PSG_MUL64(r, 0xD2511F53u, b0);
+    const uint64_t pa1 = PSG_MUL64(r, 0xCD9E8D57u, a2);
+    const uint64_t pb1 = PSG_MUL64(r, 0xCD9E8D57u, b2);
+    const uint32_t na0 = xor3((uint32_t)(pa1 >> 32), a1, k0);
+    const uint32_t nb0 = xor3((uint32_t)(pb1 >> 32), b1, k0);
+    const uint32_t na2 = xor3((uint32_t)(pa0 >> 32), a3, k1);
+    const uint32_t nb2 = xor3((uint32_t)(pb0 >> 32), b3, k1);
+    a1 = (uint32_t)pa1;
+    b1 = (uint32_t)pb1;
+    a3 = (uint32_t)pa0;
+    b3 = (uint32_t)pb0;
+    a0 = na0;
+    b0 = nb0;
+    a2 = na2;
+    b2 = nb2;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  oa = U4{a0, a1, a2, a3};
+  ob = U4{b0, b1, b2, b3};
 }
 
 // 64-bit word j of a stream: call s = j/2 with ctr3 = base + (s << 16).
@@ -985,6 +1025,25 @@ struct Sched {
     }
   }
 
+  // setup() of a seeded launch whose schedule is plain (args.crash_fmax < 0 and args.ho_min < 0,
+  // the launcher's choice): crash_on and ho_min are compile-time constants of the caller.
+  PSG_DEV void setup_plain(const KArgs& args, uint64_t i) {
+    static_assert(!XHO, "a seeded schedule");
+    hop = nullptr;
+    nproc = args.n;
+    seed = args.seed;
+    inst = i;
+    V = args.V;
+    drop = args.drop_log2;
+    good_p32 = args.good_p32;
+    self_bit = args.self_bit;
+    ho_min = -1;
+    full = mfull<W>(args.n);
+    crash_on = false;
+    good_min = args.good_min >= 0 ? args.good_min : (2 * args.n) / 3;
+    crash_round = -1;
+  }
+
   // Crash round of process pid (-1 = correct) from the instance's two crash words
   // w0, w1 (round ROUND_CRASH, pid PID_GLOBAL, words 0 and 1): f = the number of
   // crashed processes, an affine permutation of the pids picks them.
@@ -1168,6 +1227,60 @@ struct Sched {
     draw<SKIP>((uint32_t)k, (uint32_t)pid, good, crash_on && cw != 0u, dm, hf, cw);
     return assemble(pid, good, goodS, CB, CN, dm, hf);
   }
+
+  // The AND of words 0 .. NW - 1 (NW in 1..4) of pid's stream in round k, straight-line: one
+  // Philox call for NW <= 2, else calls 0 and 1 as one interleaved pair (philox10_pair). A word
+  // that is not read leaves its last-round product to the compiler to drop.
+  template <int NW>
+  PSG_DEV uint64_t and_words(uint32_t k, uint32_t pid) const {
+    if constexpr (NW <= 2) {
+      const U4 o = philox10((uint32_t)inst, (uint32_t)(inst >> 32), k, pid, (uint32_t)seed, (uint32_t)(seed >> 32));
+      uint64_t m = (uint64_t)o.x | ((uint64_t)o.y << 32);
+      if constexpr (NW == 2) m &= (uint64_t)o.z | ((uint64_t)o.w << 32);
+      return m;
+    } else {
+      U4 o, q;
+      philox10_pair((uint32_t)inst, (uint32_t)(inst >> 32), k, pid, pid + (1u << 16), (uint32_t)seed,
+                    (uint32_t)(seed >> 32), o, q);
+      uint64_t m = ((uint64_t)o.x | ((uint64_t)o.y << 32)) & ((uint64_t)o.z | ((uint64_t)o.w << 32)) &
+                   ((uint64_t)q.x | ((uint64_t)q.y << 32));
+      if constexpr (NW == 4) m &= (uint64_t)q.z | ((uint64_t)q.w << 32);
+      return m;
+    }
+  }
+
+  // HO(pid) of round k for a plain schedule — no crashes (crash_fmax < 0) and no ho_min — at
+  // W == 1: ho()'s set, bit for bit, from the same Philox calls and words. Without
+  // crash sets and survival words the set is full & ~(AND of words 0 .. drop - 1), or the round's
+  // common set when it is good, with the self bit on either: selfw is the lane's self bit as a
+  // word (0 when self_bit is off), formed once per kernel by the caller. The calls are written
+  // out for drop <= 4 behind one uniform switch; past that, a loop of whole calls.
+  PSG_DEV Mask<1> ho_plain(uint32_t k, uint32_t pid, bool good, const Mask<1>& goodS, uint64_t selfw) const {
+    static_assert(W == 1 && !XHO, "the plain draw is the seeded W == 1 kernels'");
+    Mask<1> r;
+    if (good) {
+      r.w[0] = goodS.w[0] | selfw;
+      return r;
+    }
+    uint64_t m;
+    switch (drop) {
+      case 0: m = 0ull; break;
+      case 1: m = and_words<1>(k, pid); break;
+      case 2: m = and_words<2>(k, pid); break;
+      case 3: m = and_words<3>(k, pid); break;
+      case 4: m = and_words<4>(k, pid); break;
+      default:
+        m = ~0ull;
+        for (uint32_t c = 0; 2 * c < drop; ++c) {
+          const U4 o = philox10((uint32_t)inst, (uint32_t)(inst >> 32), k, pid + (c << 16), (uint32_t)seed,
+                                (uint32_t)(seed >> 32));
+          m &= (uint64_t)o.x | ((uint64_t)o.y << 32);
+          if (2 * c + 1 < drop) m &= (uint64_t)o.z | ((uint64_t)o.w << 32);
+        }
+    }
+    r.w[0] = (full.w[0] & ~m) | selfw;
+    return r;
+  }
 };
 
 // HO(pid) of round k: Sched::ho's set, word for word, from the same draw. Only the assembly is
@@ -1253,6 +1366,11 @@ struct Inst {
     id = instance_id(a, i);
     sc.setup(a, id, g.pid, g.valid);
     if (sc.crash_on) cs.prep(g, crl, sc.crash_round);
+  }
+  // begin_front() of a plain schedule (Sched::setup_plain): no crash draw, no crash sets
+  PSG_DEV void begin_plain(const KArgs& a, uint64_t i) {
+    id = instance_id(a, i);
+    sc.setup_plain(a, id);
   }
   // Initial value of this lane's process: host-supplied, else seeded (0 for lanes past n)
   PSG_DEV int32_t x0(const Grp<W>& g, const KArgs& a, uint64_t i, int alg) const {

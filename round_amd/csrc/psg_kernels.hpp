@@ -49,6 +49,9 @@ const void* kset_es_kernel_ptr(int W);
 const void* epsilon_kernel_ptr(int W);
 const void* tpc_kernel_ptr(int W);
 const void* lattice_kernel_ptr(int W);
+// the kernels OTR / OTR2 launch a plain schedule with (psg_device.hpp plain_schedule)
+const void* otr_plain_kernel_ptr(int W);
+const void* otr2_plain_kernel_ptr(int W);
 
 hipError_t launch_champ_selftest(const uint64_t* sets, int count, int tiebreak, int32_t* out, hipStream_t s);
 hipError_t launch_schedule(const KArgs& a, int W, int grid, uint64_t* ho_out, int32_t* crash_out, hipStream_t s);

@@ -209,10 +209,15 @@ PSG_DEV void otr_check_initial(Grp<1>& g, Checks& ck, int n, int32_t x, uint32_t
 // The seeded, trace-free W == 1 forms with the built-in checker (kFront) read their good rounds
 // from a GoodFront (psg_device.hpp): rounds 0..3 of eight batch rows from one Philox pass, later
 // rounds 32 a pass. The traced and fused forms keep Sched::prep_good.
-template <int W, bool V2, bool XHO, class SH = NoHook, bool TR = true>
+// PLAIN (kFront forms only): the launch's schedule has no crashes and no ho_min (launch_w), the
+// default HOSchedule. The HO sets come from Sched::ho_plain — the same words of the same Philox
+// calls as Sched::ho, drawn straight-line — and the crash draw, the crash sets and their terms
+// are not compiled.
+template <int W, bool V2, bool XHO, class SH = NoHook, bool TR = true, bool PLAIN = false>
 PSG_DEV void otr_body(const KArgs& a) {
   const bool tracing_on = SH::kFused || (TR && a.trace != nullptr);
   constexpr bool kFront = W == 1 && !XHO && !SH::kFused && !TR;
+  static_assert(!PLAIN || kFront, "the plain-schedule form is a seeded, trace-free W == 1 form");
   __shared__ BlockCounters bc;
   __shared__ uint64_t xb[Grp<W>::kXb];
   __shared__ int32_t crl[W > 1 ? 64 * W : 1];
@@ -229,9 +234,13 @@ PSG_DEV void otr_body(const KArgs& a) {
   const Mask<W> full = mfull<W>(n);
   const uint32_t valid01 = g.valid ? 1u : 0u;
   const int32_t ckthr = W == 1 ? otr_check_thresholds<V2>(n, g.lane) : 0;  // (W > 1: unused)
+  // PLAIN: the lane's self bit as a word of the HO set, 0 when the schedule has none
+  const uint64_t selfw = PLAIN && a.self_bit ? 1ull << (g.pid & 63) : 0ull;
 
   // profiling builds only: t1 active round, t2 frozen round; the setup is t4 queue take, t5 begin +
-  // initial value, t6 X0 set, t0 check point 0; the finish t7 digest and its sum, t3 the rest
+  // initial value, t6 X0 set, t0 check point 0; the finish t7 digest and its sum, t3 the rest.
+  // Inside an active round: t8 the settled test and the good-round lookup, t9 HO draw + mailbox,
+  // t10 mmor, t11 update + countdown, and t1 is left with the round's check point.
   PhaseTimers pt;
   pt.start();
   InstanceQueue<W, 0, W == 1 ? PSG_QUEUE_CHUNK_LANE : 0> Q;  // dynamic instance distribution (psg_device.hpp)
@@ -255,7 +264,8 @@ PSG_DEV void otr_body(const KArgs& a) {
     pt.mark(4);
     Inst<W, XHO> in;
     if constexpr (kFront) {
-      in.begin_front(g, a, i, crl);
+      if constexpr (PLAIN) in.begin_plain(a, i);
+      else in.begin_front(g, a, i, crl);
       if (a.good_p32 != 0) gf.start(in.sc, a, i, g.lane);
     } else {
       in.begin(g, a, i, crl);
@@ -328,11 +338,18 @@ PSG_DEV void otr_body(const KArgs& a) {
         pt.add(4, good ? 1u : 0u);  // event build: good rounds executed unsettled
         pt.add(5, good && !good_read ? 1u : 0u);  // ... the first of them in an instance
         if (PSG_PHASE_TIMERS == 2) good_read = good_read || good;
-        Mask<W> CB = mzero<W>(), CN = mzero<W>();
-        if (sc.crash_on) in.cs.sets(g, k, CB, CN);
+        pt.mark(8);
         // mailbox: broadcast(x) from every alive sender in HO(p)
-        const Mask<W> M = mand(sc.ho(k, g.pid, good, goodS, CB, CN), act);
+        Mask<W> M;
+        if constexpr (PLAIN) {
+          M = mand(sc.ho_plain((uint32_t)k, (uint32_t)g.pid, good, goodS, selfw), act);
+        } else {
+          Mask<W> CB = mzero<W>(), CN = mzero<W>();
+          if (sc.crash_on) in.cs.sets(g, k, CB, CN);
+          M = mand(sc.ho(k, g.pid, good, goodS, CB, CN), act);
+        }
         const int32_t msize = mpopc(M);
+        pt.mark(9);
         if (tracing_on) hs = halted01 ? n : msize;
         const uint32_t upd = (1u - halted01) & gt01(msize, thr);
         if (g.any(upd != 0u)) {
@@ -384,6 +401,7 @@ PSG_DEV void otr_body(const KArgs& a) {
             rem = stage == 0 ? passB : passS;
             ++stage;
           }
+          pt.mark(10);
           const int32_t best_c = (int32_t)(best >> 32);
           const int32_t best_v = (int32_t)((uint32_t)best ^ 0x7FFFFFFFu);
           // x = mmor; decide on > 2n/3 copies, callback only the first time (Otr.scala:64-73)
@@ -404,6 +422,7 @@ PSG_DEV void otr_body(const KArgs& a) {
         halt_round = h ? k : halt_round;
         halted01 |= h;
       }
+      pt.mark(11);
       if constexpr (!SH::kFused)
         otr_check<W, V2>(g, L, X0, ck, k + 1, true, n, full, x, dec01, decision, old01, old_decision, valid01, od, ox, ckthr);
       if (tracing_on) trace(k + 1, hs);
@@ -443,11 +462,23 @@ otr_kernel(KArgs a) {
   otr_body<W, V2, XHO, SH, TR>(a);
 }
 
+// otr_kernel<1, V2, false, NoHook, false> for a plain schedule (otr_body's PLAIN); a kernel of its
+// own name, so that every other instantiation keeps its symbol. 7 waves per SIMD: the interleaved
+// pair of Sched::and_words fits the step at 72 VGPRs
+template <bool V2>
+__global__ void __launch_bounds__(Geometry<1>::kThreads) __attribute__((amdgpu_waves_per_eu(7)))
+otr_plain_kernel(KArgs a) {
+  otr_body<1, V2, false, NoHook, false, true>(a);
+}
+
 #ifndef PSG_FUSED_MODULE  // host launchers (not part of a fused Spec module)
 template <int W, bool V2>
 static hipError_t launch_w(const KArgs& a, int grid, hipStream_t s) {
   if (a.ho_in) return launch_grp<W>(otr_kernel<W, V2, true>, a, grid, s);
   if (a.trace) return launch_grp<W>(otr_kernel<W, V2, false>, a, grid, s);
+  if constexpr (W == 1) {  // the default HOSchedule: no crashes, no ho_min
+    if (plain_schedule(a)) return launch_grp<W>(otr_plain_kernel<V2>, a, grid, s);
+  }
   return launch_grp<W>(otr_kernel<W, V2, false, NoHook, false>, a, grid, s);
 }
 
@@ -456,15 +487,20 @@ static hipError_t launch_v(const KArgs& a, int W, int grid, hipStream_t s) {
   return with_w(W, hipErrorInvalidValue, [&](auto w) { return launch_w<w(), V2>(a, grid, s); });
 }
 
+// The kernel a seeded, trace-free launch of this schedule goes to (launch_w's choice): the one
+// the resident-block count is taken from.
 template <bool V2>
-static const void* ptr_v(int W) {
+static const void* ptr_v(int W, bool plain) {
+  if (W == 1 && plain) return (const void*)otr_plain_kernel<V2>;
   return with_w(W, (const void*)nullptr, [](auto w) { return (const void*)otr_kernel<w(), V2, false, NoHook, false>; });
 }
 
 hipError_t launch_otr(const KArgs& a, int W, int grid, hipStream_t s) { return launch_v<false>(a, W, grid, s); }
 hipError_t launch_otr2(const KArgs& a, int W, int grid, hipStream_t s) { return launch_v<true>(a, W, grid, s); }
-const void* otr_kernel_ptr(int W) { return ptr_v<false>(W); }
-const void* otr2_kernel_ptr(int W) { return ptr_v<true>(W); }
+const void* otr_kernel_ptr(int W) { return ptr_v<false>(W, false); }
+const void* otr2_kernel_ptr(int W) { return ptr_v<true>(W, false); }
+const void* otr_plain_kernel_ptr(int W) { return ptr_v<false>(W, true); }
+const void* otr2_plain_kernel_ptr(int W) { return ptr_v<true>(W, true); }
 
 #endif  // PSG_FUSED_MODULE
 
