@@ -160,6 +160,44 @@ PSG_DEV bool otr_check_settled(Grp<W>& g, OtrLds<W>& L, Checks& ck, int c, int n
   return true;
 }
 
+// Group size of the frozen tail in otr_body: 2, 4, 8 and 4 with a 2 for the remainder were
+// measured, 8 is the fastest.
+constexpr int kFrozenGroup = 8;
+
+// U check points of the frozen tail, c0 .. c0 + U - 1 (W == 1), as one straight-line group:
+// otr_check_settled with the frozen tail's irr01 = 0 at each of them — its own read of process
+// 0's decision, its own witness word and ballot, its own vote count and its own record — with
+// one branch for the group on the OR of the U witness ballots. The U chains do not depend on
+// one another, so they interleave. Returns false, with nothing recorded, when some check point
+// of the group is not settled (the frozen state is the same at all of them: then none is).
+// Each check point reads process 0's decision from an opaque copy of the decision that takes the
+// check-point number as an input: otherwise the U chains are one common subexpression. The
+// copies are made one from the other and the last is handed back as the decision (the same
+// value), so each copy's source dies where the copy is made and the copy is no instruction.
+template <int U, bool V2>
+PSG_DEV bool otr_check_frozen_group(Grp<1>& g, Checks& ck, int c0, int32_t x, uint32_t dec01, int32_t& decision,
+                                    uint32_t valid01, uint32_t od, uint32_t ox, int32_t ckthr) {
+  int32_t p0[U];
+  int32_t d = decision;
+#pragma unroll
+  for (int j = 0; j < U; ++j) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+v"(d) : "s"(c0 + j));
+#endif
+    p0[j] = readlane32(d, 0);
+  }
+  decision = d;
+  uint32_t u0 = (1u - dec01) | od;
+  if constexpr (!V2) u0 |= ox;  // keepInit (OTR only)
+  uint64_t wit = 0;
+#pragma unroll
+  for (int j = 0; j < U; ++j) wit |= g.ballot(((u0 | ne01(d, p0[j])) & valid01) != 0u).w[0];
+  if (wit != 0) return false;
+#pragma unroll
+  for (int j = 0; j < U; ++j) ck.record_le(mpopc(g.ballot(x == p0[j])), ckthr, c0 + j);
+  return true;
+}
+
 template <int W, bool V2, bool FROZEN = false>
 // od / ox: "decision / x maybe not initial" (X0Set::maybe_out01_2 of the current values), probed
 // by the caller when the values change (round 0 and executed updates) instead of at every check
@@ -431,7 +469,23 @@ PSG_DEV void otr_body(const KArgs& a) {
     // Rounds kf .. R-1: every process has halted, so no process takes a step and the state, the
     // pre-round (old) state included, is the final one; the Spec is still evaluated at each of
     // these check points, kf + 1 .. R (Otr.scala:95-120 over the frozen state).
-    for (int k = kf; k < a.R; ++k) {
+    // W == 1 with the built-in checker and no trace: in groups of kFrozenGroup check points
+    // (otr_check_frozen_group) while that many are left and the state is settled; the rest of the
+    // tail — the remainder, or all of it from a group that found the state unsettled, which a
+    // frozen state then stays — goes through the loop below. The seeded TR form is not among
+    // them: launch_w sends it traced launches only, and it keeps the code it had (with the groups
+    // compiled in and never run, its G1 row measured 0.6 % slower).
+    int kt = kf;
+    if constexpr (W == 1 && !SH::kFused && (XHO || !TR)) {
+      if (!tracing_on) {
+        while (kt + kFrozenGroup <= a.R &&
+               otr_check_frozen_group<kFrozenGroup, V2>(g, ck, kt + 1, x, dec01, decision, valid01, od, ox, ckthr)) {
+          kt += kFrozenGroup;
+          pt.mark(2);
+        }
+      }
+    }
+    for (int k = kt; k < a.R; ++k) {
       if constexpr (!SH::kFused)
         otr_check<W, V2, true>(g, L, X0, ck, k + 1, true, n, full, x, dec01, decision, dec01, decision, valid01, od, ox, ckthr);
       if (tracing_on) trace(k + 1, n, true);
