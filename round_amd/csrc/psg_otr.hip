@@ -240,6 +240,79 @@ PSG_DEV void otr_check_initial(Grp<1>& g, Checks& ck, int n, int32_t x, uint32_t
   ck.record(fb, false, 0, g.lane);
 }
 
+// mmor (max multiplicity, ties to the smaller value: OtrExample.scala:67-75) of one W == 1 round
+// in bitmap mode (X0.bmode): every initial value lies in [lo, lo + 64), and every later x is a
+// value some process received, i.e. the x of a sender, so by induction over the rounds every
+// alive process's x stays in that window. best_c / best_v: the winning count and value of this
+// lane's mailbox M (meaningful on the updating lanes, whose mailbox is not empty).
+// - A value v is named by its complement slot c = 63 - (v - lo) in 0..63, and the running best is
+//   one 32-bit key, count << 6 | c (count <= 64): a larger key has a larger count, or the same
+//   count and a smaller value, so folding a value is one unsigned max. The one uniform c serves
+//   the compare that finds the value's holders E and the key's low bits; count and value are
+//   decoded once after the loop. (Unsigned arithmetic throughout: lo + 63 may pass INT32_MAX.)
+//   Lanes past n hold x = 0 and may match a c; E is only ever intersected with M, inside act.
+// - Round 0: every process is alive and holds its initial value, so the distinct values are
+//   exactly the bits of X0.bm. They are walked on the scalar pipe (find first bit, clear it): no
+//   lane is read and no ballot feeds the walk, so the trips depend on one another only through
+//   the max. One value a trip: two a trip (the last bit folded twice when one is left) measured
+//   0.9 % slower on the headline.
+//   With more than 8 distinct values (V = 64: ~40 of 64) they are folded by decreasing holder
+//   classes, as value bitmaps: a value held by h alive senders counts at most h in any mailbox,
+//   so h >= 3 goes first, then h = 2, then h = 1, and a class is skipped when every updating
+//   lane's best count already exceeds its h (it can neither win nor tie). Holders are counted in
+//   LDS (cnt: 64 words, the X0 table, free in bitmap mode), lane b reads the count of value lo + b
+//   behind a wave-scope fence.
+// - Rounds k > 0 have few values and no bitmap of them: the walk over the alive lanes' values
+//   (read the first remaining lane's c, drop its holders), with the same key.
+PSG_DEV void otr_mmor_bitmap(Grp<1>& g, const X0Set<1>& X0, int32_t* cnt, int k, int32_t x, const Mask<1>& M,
+                             const Mask<1>& act, uint32_t upd, uint32_t halted01, int32_t& best_c, int32_t& best_v) {
+  const uint32_t cs = 63u - ((uint32_t)x - (uint32_t)X0.lo);
+  const uint64_t m = M.w[0];
+  auto key = [&](uint32_t c) -> uint32_t {
+    const uint64_t E = __builtin_amdgcn_ballot_w64(cs == c);
+    return ((uint32_t)__builtin_popcountll(m & E) << 6) | c;
+  };
+  auto umax = [](uint32_t p, uint32_t q) -> uint32_t { return p > q ? p : q; };
+  uint32_t best = 0;
+  if (k == 0) {
+    uint64_t B = X0.bm, passB = 0, passS = 0;
+    int stage = 2;  // 2: a single pass over every value
+    if (__builtin_popcountll(B) > 8) {
+      cnt[g.lane] = 0;
+      if (!halted01) atomicAdd(&cnt[63u - cs], 1);
+      lds_sync<1>();  // lane b reads what the other lanes added (without it its own 0 is forwarded)
+      const int32_t h = cnt[g.lane];
+      B = __builtin_amdgcn_ballot_w64(h >= 3);
+      passB = __builtin_amdgcn_ballot_w64(h == 2);
+      passS = X0.bm & ~(B | passB);
+      stage = 0;
+    }
+    while (true) {
+      while (B != 0) {
+        const uint32_t b = (uint32_t)__builtin_ctzll(B);
+        B &= ~(1ull << b);  // (shift and and-not: B & (B - 1) is three scalar instructions)
+        // c behind an opaque copy: folded into the key's arithmetic it costs a VALU a value
+        best = umax(key(opaque_uniform(63u ^ b)), best);
+      }
+      if (stage == 2) break;
+      const uint32_t beat = stage == 0 ? 3u : 2u;  // the next class's values count < beat
+      if (!g.any(upd != 0u && best < (beat << 6))) break;
+      B = stage == 0 ? passB : passS;
+      ++stage;
+    }
+  } else {
+    uint64_t rem = act.w[0];
+    while (rem != 0) {
+      const uint32_t c = (uint32_t)readlane32((int32_t)cs, __builtin_ctzll(rem));
+      const uint64_t E = __builtin_amdgcn_ballot_w64(cs == c);
+      rem &= ~E;
+      best = umax(((uint32_t)__builtin_popcountll(m & E) << 6) | c, best);
+    }
+  }
+  best_c = (int32_t)(best >> 6);
+  best_v = (int32_t)((uint32_t)X0.lo + 63u - (best & 63u));
+}
+
 // Kernel body; SH: the Spec hook (NoHook in psg_device.hpp). TR = false: the launch has no
 // Spec-program trace (a.trace == nullptr), known at compile time.
 // W == 1 takes its own forms of the per-instance setup and finish: X0Set::build_window,
@@ -247,6 +320,8 @@ PSG_DEV void otr_check_initial(Grp<1>& g, Checks& ck, int n, int32_t x, uint32_t
 // The seeded, trace-free W == 1 forms with the built-in checker (kFront) read their good rounds
 // from a GoodFront (psg_device.hpp): rounds 0..3 of eight batch rows from one Philox pass, later
 // rounds 32 a pass. The traced and fused forms keep Sched::prep_good.
+// The kFront forms also run mmor through otr_mmor_bitmap when the instance's values fit a 64-value
+// window (X0.bmode); hash mode and the other forms keep the loop in the body.
 // PLAIN (kFront forms only): the launch's schedule has no crashes and no ho_min (launch_w), the
 // default HOSchedule. The HO sets come from Sched::ho_plain — the same words of the same Philox
 // calls as Sched::ho, drawn straight-line — and the crash draw, the crash sets and their terms
@@ -391,6 +466,15 @@ PSG_DEV void otr_body(const KArgs& a) {
         if (tracing_on) hs = halted01 ? n : msize;
         const uint32_t upd = (1u - halted01) & gt01(msize, thr);
         if (g.any(upd != 0u)) {
+          int32_t best_c = 0, best_v = 0;
+          bool folded = false;
+          if constexpr (kFront) {
+            if (X0.bmode) {
+              otr_mmor_bitmap(g, X0, x0tab[grp], k, x, M, act, upd, halted01, best_c, best_v);
+              folded = true;
+            }
+          }
+          if (!folded) {
           // mmor: max multiplicity, ties -> smaller value (OtrExample.scala:67-75).
           // The running best is one 64-bit key (count << 32 | v ^ 0x7FFFFFFF): a larger
           // key has a larger count, or the same count and a smaller v, so one 64-bit
@@ -439,9 +523,10 @@ PSG_DEV void otr_body(const KArgs& a) {
             rem = stage == 0 ? passB : passS;
             ++stage;
           }
+          best_c = (int32_t)(best >> 32);
+          best_v = (int32_t)((uint32_t)best ^ 0x7FFFFFFFu);
+          }  // !folded
           pt.mark(10);
-          const int32_t best_c = (int32_t)(best >> 32);
-          const int32_t best_v = (int32_t)((uint32_t)best ^ 0x7FFFFFFFu);
           // x = mmor; decide on > 2n/3 copies, callback only the first time (Otr.scala:64-73)
           x = upd ? best_v : x;
           const uint32_t newdec = upd & gt01(best_c, thr);
