@@ -516,6 +516,56 @@ int psg_population_read_crash(psg_ctx* ctx, const uint32_t* rows, size_t k, int3
  * 2n/3; coord hears all: HO((k / phase) % n, k) is everyone; fixed coord: slot k % phase == 1, HO(coord)
  * is everyone, slot 2, every HO(p) contains coord, other slots hold. */
 int psg_population_live(psg_ctx* ctx, int32_t live_kind, int32_t phase, int32_t coord, uint8_t* live);
+/* links [count] uint32: the links present in instance i of the loaded explicit schedule (a population,
+ * psg_load_schedule's or psg_shrink_load's; count = its instance count): the sum of |HO(p, k)| over its
+ * rounds and processes, bits >= n ignored. */
+int psg_population_links(psg_ctx* ctx, uint32_t* links);
+
+/* Shrinking a counterexample on the device: the candidate simplifications of one step of
+ * Adversary.shrink (round_amd/adversary.py) are written into HBM as the loaded explicit schedule, so
+ * no HO set crosses PCIe until the shrunk schedule is read back. Single-device contexts, int32 inputs
+ * (not EpsilonConsensus).
+ *
+ * The base is one schedule ho [R][n][W] (bits >= n are cleared on entry), its crash rounds [n]
+ * (nullable) and initial values [n], resident on the device. Every candidate of a level is the base
+ * with one edit, in the host's order:
+ *   TAIL   arg = check point c: one candidate, the rounds k >= c made full (also when that changes
+ *          nothing; c >= R: the base itself)
+ *   ROUND  for k ascending with some HO(p, k) not full: round k made full
+ *   SET    for (k, p) ascending with HO(p, k) not full: that set made full
+ *   LINK   arg = max_candidates (0: no cap): for (k, p) ascending, q ascending with q not in HO(p, k):
+ *          q added; the enumeration ends after the first set (k, p) whose links bring the count above
+ *          max_candidates
+ *   CRASH  arg = self bit (0 / 1), a base with crash rounds: for q ascending with crash(q) >= 0, q
+ *          correct; then for q ascending with crash(q) >= 0 and crash(q) + 1 < R, q crashing one round
+ *          later. The candidate's HO sets are the crash family's (psg_population_fresh_model) for its
+ *          crash rounds, with partial(p) = the q in HO(p, crash(q)) of the base over the crashed q.
+ * Below CRASH a candidate keeps the base's crash rounds. */
+enum psg_shrink_level {
+  PSG_SHRINK_TAIL = 0,
+  PSG_SHRINK_ROUND = 1,
+  PSG_SHRINK_SET = 2,
+  PSG_SHRINK_LINK = 3,
+  PSG_SHRINK_CRASH = 4
+};
+/* Set the base (ho [R][n][W], crash_round [n] nullable, init [n]). */
+int psg_shrink_begin(psg_ctx* ctx, const uint64_t* ho, const int32_t* crash_round, const int32_t* init);
+/* *total = the number of candidates of the level over the base. */
+int psg_shrink_count(psg_ctx* ctx, int32_t level, uint32_t arg, uint64_t* total);
+/* Load candidates [first, first + count) of the level as instances [inst_begin, inst_begin + count)
+ * (count <= batch_capacity, 0 allowed): afterwards the context is exactly as after psg_load_inputs
+ * (the base's initial values in every row) + psg_load_schedule (the candidates' sets and crash
+ * rounds); not a crash-family population (psg_population_read_crash: PSG_EINVAL). */
+int psg_shrink_load(psg_ctx* ctx, int32_t level, uint32_t arg, uint64_t first, uint64_t count, uint64_t inst_begin);
+/* The base becomes candidate j of the level (whether or not it is loaded). */
+int psg_shrink_adopt(psg_ctx* ctx, int32_t level, uint32_t arg, uint64_t j);
+/* The base: ho [R][n][W], crash_round [n] (nullable; -1 everywhere for a base without crash rounds). */
+int psg_shrink_read(psg_ctx* ctx, uint64_t* ho, int32_t* crash_round);
+/* Errors of psg_shrink_* change nothing: PSG_EINVAL for no base, an unknown level, CRASH over a base
+ * without crash rounds, a crash round outside -1..R-1, a device-list context, EpsilonConsensus;
+ * PSG_ERANGE for count > batch_capacity, first + count > total, j >= total. The exception is a
+ * failure of the HIP runtime itself (PSG_EIO, PSG_ENOMEM): psg_shrink_begin then leaves the context
+ * without a base, and a load or adoption it interrupts leaves its target undefined. */
 
 const char* psg_last_error(const psg_ctx* ctx);
 void psg_destroy(psg_ctx* ctx);

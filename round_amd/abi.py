@@ -238,6 +238,8 @@ class PopulationParams(C.Structure):
 PSG_POP_OMISSION, PSG_POP_CRASH = 0, 1
 PSG_LIVE_NONE, PSG_LIVE_GOOD_ROUND, PSG_LIVE_COORD_HEARS_ALL, PSG_LIVE_FIXED_COORD = 0, 1, 2, 3
 PSG_POP_MAX_LIVE = 8
+# enum psg_shrink_level
+PSG_SHRINK_TAIL, PSG_SHRINK_ROUND, PSG_SHRINK_SET, PSG_SHRINK_LINK, PSG_SHRINK_CRASH = 0, 1, 2, 3, 4
 
 
 class PopulationModel(C.Structure):

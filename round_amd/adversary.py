@@ -27,8 +27,10 @@ with device_models=True.)
     BenOr, EpsilonConsensus, TwoPhaseCommit, LatticeAgreement) or crash-stop with at most f crashes (FloodMin,
     KSetAgreement, KSetEarlyStopping — their runners' fault model).
 Every counterexample is shrunk (batched delta debugging: all candidate
-simplifications of one step run as one GPU batch) and can be written to a
-.psgr file (round_amd/records.py) that `records.replay` re-executes.
+simplifications of one step run as one GPU batch; with device_shrink=True the
+candidates are written on the device too, psg_shrink_*, and only the shrunk
+schedule comes back) and can be written to a .psgr file (round_amd/records.py)
+that `records.replay` re-executes.
 """
 import time
 from dataclasses import dataclass, field
@@ -94,6 +96,11 @@ class Model:
     liveness: Optional[str] = None   # "good_round" | "coord_hears_all" | "fixed_coord"
     phase: int = 4                   # coordinator period (coord = (r / phase) % n)
     coord: int = 0                   # "fixed_coord": the coordinator of every phase
+
+
+# Model.liveness -> enum psg_pop_live
+LIVE_KIND = {"good_round": abi.PSG_LIVE_GOOD_ROUND, "coord_hears_all": abi.PSG_LIVE_COORD_HEARS_ALL,
+             "fixed_coord": abi.PSG_LIVE_FIXED_COORD}
 
 
 def default_model(alg: psync.Algorithm, n: int) -> Model:
@@ -172,7 +179,7 @@ class Adversary:
                  population: int = 4096, values: int = 3, keep: float = 0.75, self_bit: bool = True,
                  live_rounds: int = 2, live_at: Optional[Sequence[int]] = None, seed: int = 1,
                  evaluator: Optional[Callable] = None, device: int = 0, device_pop: bool = True,
-                 device_models: bool = False):
+                 device_models: bool = False, device_shrink: bool = False):
         if mode not in ("safety", "liveness"):
             raise ValueError("mode must be 'safety' or 'liveness'")
         self.alg, self.n, self.R = alg, n, rounds
@@ -194,6 +201,8 @@ class Adversary:
         self.live_at = None if live_at is None else list(live_at)
         self.device_pop = device_pop
         self.device_models = device_models
+        self.device_shrink = device_shrink
+        self.shrink_stats = {"steps": 0, "batches": 0, "candidates": 0}  # of the last shrink_device call
         self.rng = np.random.default_rng(seed)
         self._own = evaluator is None
         self.evaluator = evaluator or GpuEvaluator(alg, n, rounds, population, device=device,
@@ -350,8 +359,7 @@ class Adversary:
             pm.move_p256, pm.add_p256, pm.drop_p256 = 77, 77, 38  # schedules.mutate_crash: 0.3, 0.3, 0.15
             return pm
         pm.family = abi.PSG_POP_OMISSION
-        pm.live_kind = {"good_round": abi.PSG_LIVE_GOOD_ROUND, "coord_hears_all": abi.PSG_LIVE_COORD_HEARS_ALL,
-                        "fixed_coord": abi.PSG_LIVE_FIXED_COORD}[m.liveness]
+        pm.live_kind = LIVE_KIND[m.liveness]
         pm.live_rounds = self.live_rounds
         for j in range(self.live_rounds):
             pm.live_at[j] = -1 if self.live_at is None else self.live_at[j % len(self.live_at)]
@@ -432,7 +440,7 @@ class Adversary:
             gpu += time.perf_counter() - t1
         secs = time.perf_counter() - t0
         if shrink:
-            found = [self.shrink(c) for c in found]
+            found = [self._shrink(c) for c in found]
         return SearchResult(found, P * g, g, secs, gpu, history)
 
     def search(self, generations: int = 50, want: int = 1, time_budget: Optional[float] = None,
@@ -483,7 +491,7 @@ class Adversary:
             init = np.concatenate([init[elite], cinit, default_init(self.alg, self.rng, nf, self.n, self.values)])
         secs = time.perf_counter() - t0
         if shrink:
-            found = [self.shrink(c) for c in found]
+            found = [self._shrink(c) for c in found]
         return SearchResult(found, evaluated, g, secs, gpu, history)
 
     def _cex(self, inst, init, ho, crash, summ, first):
@@ -637,6 +645,92 @@ class Adversary:
                 if not accept(hh, None):
                     break
         return cur
+
+    def _shrink(self, c: Counterexample) -> Counterexample:
+        """search(shrink=True): on the device when device_shrink is set and available."""
+        if self.device_shrink and self.device_shrink_available():
+            return self.shrink_device(c)
+        return self.shrink(c)
+
+    def device_shrink_available(self) -> bool:
+        """Can shrink steps run on the GPU (psg_shrink_*)? The GPU evaluator (one device), integer
+        inputs, not BenOr: its coins are keyed by the instance id, so its candidates run one by one."""
+        return isinstance(self.evaluator, GpuEvaluator) and not self.alg.real and \
+            self.alg.alg_id != abi.PSG_ALG_BENOR
+
+    def shrink_device(self, c: Counterexample, max_steps: int = 64) -> Counterexample:
+        """shrink() with the candidates of every step written on the device (psg_shrink_load) from
+        a base schedule resident there: the same levels, candidate order, cap, step accounting and
+        selection, so the same counterexample bit for bit. Per chunk of `population` candidates
+        only the per-instance summaries, the link counts and (liveness) the live rounds come to
+        the host; the HO sets come once, at the end. In liveness mode every candidate of a list is
+        evaluated and the ones with too few live rounds are then left out of the choice, where the
+        host drops them before it evaluates: shrink_stats["candidates"] counts them, so it can
+        exceed the host's count (the result does not change)."""
+        if not self.device_shrink_available():
+            raise ValueError("shrink_device needs the GPU evaluator, integer inputs and an algorithm other than BenOr")
+        ctx = self.evaluator.gr._ctx
+        m, P = self.model, self.population
+        ctx.shrink_begin(c.ho, c.crash, c.init)
+        cur = c           # (its ho / crash / omitted_links are filled in from the device at the end)
+        accepted = False
+        steps = batches = evaluated = 0
+        lowest = np.iinfo(np.int64).min
+
+        def step(level, arg):
+            """One batch of candidates over the base; adopts the host's choice. False: no candidate
+            (left after the liveness filter) or none still bad."""
+            nonlocal cur, accepted, batches, evaluated
+            total = ctx.shrink_count(level, arg)
+            batches += total > 0
+            best = None  # (key, index, summary, first) of the first maximum so far
+            any_bad = False
+            for a in range(0, total, P):
+                k = min(P, total - a)
+                ctx.shrink_load(level, arg, a, k, cur.inst_id)  # every candidate replays the counterexample's id
+                _, pi = ctx.run_batch_np(cur.inst_id, k)
+                evaluated += k
+                bad, first = self._violations(Eval(pi, None, None))
+                links = ctx.population_links().astype(np.int64)
+                key = np.where(bad, links * 1024 - first, -1)
+                if self.mode == "liveness":  # the host drops these candidates before it evaluates
+                    live = ctx.population_live(LIVE_KIND[m.liveness], m.phase, m.coord)
+                    valid = live.sum(1) >= self.live_rounds
+                    bad &= valid
+                    key[~valid] = lowest
+                any_bad |= bool(bad.any())
+                j = int(np.argmax(key))
+                if key[j] > (lowest if best is None else best[0]):
+                    best = (int(key[j]), a + j, pi[j].copy(), int(first[j]))
+            if not any_bad:
+                return False
+            _, j, summ, first = best
+            ctx.shrink_adopt(level, arg, j)
+            viol = cur.violated if self.mode == "liveness" else \
+                [self.names[t] for t in self.targets if summ["first_fail"][t] == first]
+            cur = Counterexample(cur.inst_id, cur.init, cur.ho, cur.crash, summ, viol, first, cur.omitted_links)
+            accepted = True
+            return True
+
+        if m.family == "crash":
+            while steps < max_steps:
+                steps += 1
+                if not step(abi.PSG_SHRINK_CRASH, 1 if self.self_bit else 0):
+                    break
+        else:
+            if self.mode == "safety" and cur.check_point < NEVER:
+                step(abi.PSG_SHRINK_TAIL, cur.check_point)
+            for level, arg in ((abi.PSG_SHRINK_ROUND, 0), (abi.PSG_SHRINK_SET, 0), (abi.PSG_SHRINK_LINK, 4 * P)):
+                while steps < max_steps:
+                    steps += 1
+                    if not step(level, arg):
+                        break
+        self.shrink_stats = {"steps": steps, "batches": batches, "candidates": evaluated}
+        if not accepted:
+            return c
+        ho, crash = ctx.shrink_read()
+        return Counterexample(cur.inst_id, cur.init, ho, crash, cur.summary, cur.violated, cur.check_point,
+                              self._omitted(ho))
 
 
 # ------------------------------------------------------------------ files

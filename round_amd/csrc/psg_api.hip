@@ -103,6 +103,13 @@ struct psg_buffers {
   DevBuf<int32_t> d_crash2;
   DevBuf<uint64_t> d_partial, d_partial2;
   DevBuf<uint8_t> d_live;
+  // shrinking (psg_shrink_*): the base schedule [R][n][W], its crash rounds and initial values [n],
+  // its crash-round deliveries [n][W], the level's prefix, a chunk's edits; psg_population_links' output
+  DevBuf<uint64_t> d_sh_base, d_sh_part;
+  DevBuf<int32_t> d_sh_crash, d_sh_init;
+  DevBuf<uint32_t> d_sh_pre;
+  DevBuf<ShrinkEdit> d_sh_edit;
+  DevBuf<uint32_t> d_links;
   DevBuf<int32_t> d_dec;
   DevBuf<uint8_t> d_dround;
   DevBuf<psg_instance_summary> d_inst;
@@ -133,6 +140,11 @@ struct psg_ctx : psg_buffers {
   bool ho_loaded = false, ho_has_crash = false;
   bool pop_crash = false;  // the loaded schedule is a crash-family population (its genome is on the device)
   uint64_t ho_begin = 0, ho_count = 0;
+  // shrink base (psg_shrink_begin), and the (level, arg) whose prefix d_sh_pre holds with its total
+  bool sh_base = false, sh_has_crash = false, sh_counted = false;
+  int32_t sh_level = 0;
+  uint32_t sh_arg = 0;
+  uint64_t sh_total = 0;
   uint64_t last_count = 0;
   int grid_max = 0;  // resident blocks for the algorithm's kernel
   std::string err;
@@ -1601,6 +1613,198 @@ int psg_population_read(psg_ctx* c, const uint32_t* rows, size_t k, uint64_t* ho
     if (init && c->staged)
       HIPCHK(c, hipMemcpy(init + j * n, c->d_init + (uint64_t)rows[j] * n, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
   }
+  return PSG_OK;
+}
+
+int psg_population_links(psg_ctx* c, uint32_t* links) {
+  if (!c) return PSG_EINVAL;
+  if (!c->subs.empty()) return fail(c, PSG_EINVAL, "device-resident populations need a single-device context");
+  if (!c->ho_loaded) return fail(c, PSG_EINVAL, "no explicit schedule loaded");
+  if (c->ho_count == 0) return PSG_OK;
+  if (!links) return fail(c, PSG_EINVAL, "null output");
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  HIPCHK(c, c->d_links.grow(c->ho_count));
+  HIPCHK(c, launch_links(c->d_ho, c->d_links, c->ho_count, c->cfg.n, c->cfg.rounds, c->W, c->stream));
+  HIPCHK(c, hipMemcpyAsync(links, c->d_links, sizeof(uint32_t) * c->ho_count, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return PSG_OK;
+}
+
+// ---------------------------------------------------------------- shrinking on the device
+// Units of a level: what its prefix runs over (ShrinkArgs::pre).
+static uint32_t shrink_units(const psg_ctx* c, int32_t level) {
+  const uint32_t n = (uint32_t)c->cfg.n, R = (uint32_t)c->cfg.rounds;
+  return level == PSG_SHRINK_TAIL ? 1u : level == PSG_SHRINK_ROUND ? R : level == PSG_SHRINK_CRASH ? 2u * n : R * n;
+}
+
+static ShrinkArgs shrink_args(const psg_ctx* c, int32_t level, uint32_t arg) {
+  ShrinkArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.base = c->d_sh_base;
+  a.base_crash = c->sh_has_crash ? (int32_t*)c->d_sh_crash : nullptr;
+  a.base_init = c->d_sh_init;
+  a.part = c->d_sh_part;
+  a.pre = c->d_sh_pre;
+  a.edit = c->d_sh_edit;
+  a.n = c->cfg.n;
+  a.R = c->cfg.rounds;
+  a.W = c->W;
+  a.level = level;
+  a.arg = arg;
+  a.units = shrink_units(c, level);
+  return a;
+}
+
+// The checks every psg_shrink_* call over a level shares, then the level's prefix (d_sh_pre) and
+// total over the base: computed once per (level, arg) and base.
+static int shrink_level(psg_ctx* c, int32_t level, uint32_t arg, uint64_t* total) {
+  if (!c->subs.empty()) return fail(c, PSG_EINVAL, "shrinking on the device needs a single-device context");
+  if (c->cfg.alg == PSG_ALG_EPSILON) return fail(c, PSG_EINVAL, "shrink bases hold int32 inputs (not EpsilonConsensus)");
+  if (!c->sh_base) return fail(c, PSG_EINVAL, "no shrink base (psg_shrink_begin first)");
+  if (level < PSG_SHRINK_TAIL || level > PSG_SHRINK_CRASH) return fail(c, PSG_EINVAL, "unknown shrink level");
+  if (level == PSG_SHRINK_CRASH && !c->sh_has_crash)
+    return fail(c, PSG_EINVAL, "PSG_SHRINK_CRASH needs a base with crash rounds");
+  if (level == PSG_SHRINK_CRASH) arg &= 1u;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  if (!(c->sh_counted && c->sh_level == level && c->sh_arg == arg)) {
+    const ShrinkArgs a = shrink_args(c, level, arg);
+    uint32_t t = 0;
+    c->sh_counted = false;
+    HIPCHK(c, launch_shrink_scan(a, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&t, c->d_sh_pre + a.units + 1, sizeof(t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->sh_counted = true;
+    c->sh_level = level;
+    c->sh_arg = arg;
+    c->sh_total = t;
+  }
+  *total = c->sh_total;
+  return PSG_OK;
+}
+
+// CRASH: the base's crash-round deliveries, then the HO sets of `count` genomes (a.crash, partial).
+static int shrink_crash_sets(psg_ctx* c, const ShrinkArgs& a, uint64_t count, int32_t* crash, uint64_t* partial,
+                             uint64_t* ho) {
+  PopArgs p;
+  std::memset(&p, 0, sizeof(p));
+  p.count = count;
+  p.n = a.n;
+  p.R = a.R;
+  p.W = a.W;
+  p.self_bit = a.arg & 1u;
+  p.crash = crash;
+  p.partial = partial;
+  p.ho = ho;
+  HIPCHK(c, launch_crash_ho(p, c->stream));
+  return PSG_OK;
+}
+
+int psg_shrink_begin(psg_ctx* c, const uint64_t* ho, const int32_t* crash_round, const int32_t* init) {
+  if (!c) return PSG_EINVAL;
+  if (!c->subs.empty()) return fail(c, PSG_EINVAL, "shrinking on the device needs a single-device context");
+  if (c->cfg.alg == PSG_ALG_EPSILON) return fail(c, PSG_EINVAL, "shrink bases hold int32 inputs (not EpsilonConsensus)");
+  if (!ho || !init) return fail(c, PSG_EINVAL, "null schedule / initial values");
+  const uint64_t n = (uint64_t)c->cfg.n, W = (uint64_t)c->W, per = sched_words(c);
+  for (uint64_t q = 0; crash_round && q < n; ++q)
+    if (crash_round[q] < -1 || crash_round[q] >= c->cfg.rounds) return fail(c, PSG_EINVAL, "crash round outside -1..R-1");
+  std::vector<uint64_t> clean(ho, ho + per);  // bits >= n cleared
+  if (c->cfg.n % 64)
+    for (uint64_t r = W - 1; r < per; r += W) clean[r] &= (1ull << (c->cfg.n % 64)) - 1ull;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  c->sh_base = c->sh_counted = false;
+  HIPCHK(c, c->d_sh_base.grow(per));
+  HIPCHK(c, c->d_sh_part.grow(n * W));
+  HIPCHK(c, c->d_sh_crash.grow(n));
+  HIPCHK(c, c->d_sh_init.grow(n));
+  HIPCHK(c, c->d_sh_pre.grow(std::max<uint64_t>((uint64_t)c->cfg.rounds * n, 2 * n) + 2));
+  HIPCHK(c, c->d_sh_edit.grow(1));
+  HIPCHK(c, hipMemcpyAsync(c->d_sh_base, clean.data(), sizeof(uint64_t) * per, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->d_sh_init, init, sizeof(int32_t) * n, hipMemcpyHostToDevice, c->stream));
+  if (crash_round)
+    HIPCHK(c, hipMemcpyAsync(c->d_sh_crash, crash_round, sizeof(int32_t) * n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->sh_base = true;
+  c->sh_has_crash = crash_round != nullptr;
+  return PSG_OK;
+}
+
+int psg_shrink_count(psg_ctx* c, int32_t level, uint32_t arg, uint64_t* total) {
+  if (!c || !total) return PSG_EINVAL;
+  return shrink_level(c, level, arg, total);
+}
+
+int psg_shrink_load(psg_ctx* c, int32_t level, uint32_t arg, uint64_t first, uint64_t count, uint64_t inst_begin) {
+  if (!c) return PSG_EINVAL;
+  uint64_t total = 0;
+  if (int rc = shrink_level(c, level, arg, &total)) return rc;
+  if (count > c->cap) return fail(c, PSG_ERANGE, "inst_count exceeds batch_capacity");
+  if (first > total || count > total - first) return fail(c, PSG_ERANGE, "candidates beyond the level's total");
+  const bool crash = level == PSG_SHRINK_CRASH;
+  if (int rc = sched_buffers(c, std::max<uint64_t>(count, 1))) return rc;
+  if (crash) HIPCHK(c, c->d_partial.grow(std::max<uint64_t>(count, 1) * (uint64_t)c->cfg.n * (uint64_t)c->W));
+  HIPCHK(c, c->d_sh_edit.grow(std::max<uint64_t>(count, 1)));
+  ShrinkArgs a = shrink_args(c, level, crash ? (arg & 1u) : arg);
+  a.first = first;
+  a.count = count;
+  a.ho = c->d_ho;
+  a.init = c->d_init;
+  a.crash = c->sh_has_crash ? (int32_t*)c->d_crash : nullptr;
+  a.partial = crash ? (uint64_t*)c->d_partial : nullptr;
+  HIPCHK(c, launch_shrink_edits(a, c->stream));
+  if (crash) {
+    HIPCHK(c, launch_shrink_part(a, c->stream));
+    HIPCHK(c, launch_shrink_rows(a, c->stream));
+    if (int rc = shrink_crash_sets(c, a, count, c->d_crash, c->d_partial, c->d_ho)) return rc;
+  } else {
+    HIPCHK(c, launch_shrink_fill(a, c->stream));
+    HIPCHK(c, launch_shrink_rows(a, c->stream));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->ho_loaded = true;
+  c->ho_has_crash = c->sh_has_crash;
+  c->pop_crash = false;
+  c->ho_begin = inst_begin;
+  c->ho_count = count;
+  set_staged(c, inst_begin, count, true);
+  return PSG_OK;
+}
+
+int psg_shrink_adopt(psg_ctx* c, int32_t level, uint32_t arg, uint64_t j) {
+  if (!c) return PSG_EINVAL;
+  uint64_t total = 0;
+  if (int rc = shrink_level(c, level, arg, &total)) return rc;
+  if (j >= total) return fail(c, PSG_ERANGE, "candidate beyond the level's total");
+  const bool crash = level == PSG_SHRINK_CRASH;
+  ShrinkArgs a = shrink_args(c, level, crash ? (arg & 1u) : arg);
+  a.first = j;
+  a.count = 1;
+  a.ho = c->d_sh_base;  // the edit in place: every word depends on its own old value only
+  c->sh_counted = false;
+  HIPCHK(c, launch_shrink_edits(a, c->stream));
+  if (crash) {
+    a.crash = c->d_sh_crash;
+    HIPCHK(c, launch_shrink_part(a, c->stream));  // from the old base, before its crash rounds move
+    HIPCHK(c, launch_shrink_rows(a, c->stream));
+    if (int rc = shrink_crash_sets(c, a, 1, c->d_sh_crash, c->d_sh_part, c->d_sh_base)) return rc;
+  } else {
+    HIPCHK(c, launch_shrink_fill(a, c->stream));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return PSG_OK;
+}
+
+int psg_shrink_read(psg_ctx* c, uint64_t* ho, int32_t* crash_round) {
+  if (!c) return PSG_EINVAL;
+  if (!c->subs.empty()) return fail(c, PSG_EINVAL, "shrinking on the device needs a single-device context");
+  if (!c->sh_base) return fail(c, PSG_EINVAL, "no shrink base (psg_shrink_begin first)");
+  if (!ho) return fail(c, PSG_EINVAL, "null output");
+  const uint64_t n = (uint64_t)c->cfg.n;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  HIPCHK(c, hipMemcpyAsync(ho, c->d_sh_base, sizeof(uint64_t) * sched_words(c), hipMemcpyDeviceToHost, c->stream));
+  if (crash_round && c->sh_has_crash)
+    HIPCHK(c, hipMemcpyAsync(crash_round, c->d_sh_crash, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (crash_round && !c->sh_has_crash) std::fill(crash_round, crash_round + n, -1);
   return PSG_OK;
 }
 

@@ -149,6 +149,38 @@ struct LiveArgs {
   int n, R, W;
   int32_t kind, phase, coord;
 };
+// Word w of the set of all n processes.
+PSG_DEV uint64_t full_word(int n, int w) {
+  const int b = n - 64 * w;
+  return b >= 64 ? ~0ull : (b <= 0 ? 0ull : ((1ull << b) - 1ull));
+}
+// Shrink kernels (psg_shrink.hip). One candidate of a level is the base schedule with one edit:
+// the words [lo, hi) of the base's [R][n][W] made full (bit == SHRINK_FULL), or bit `bit` of word
+// lo set (LINK); at CRASH `unit` names the crash edit (q: un-crash q; n + q: q crashes a round later).
+constexpr uint32_t SHRINK_FULL = 0xFFFFFFFFu;
+struct ShrinkEdit {
+  uint32_t lo, hi, bit, unit;
+};
+struct ShrinkArgs {
+  uint64_t* base;            // the base schedule [R][n][W], bits >= n clear
+  int32_t* base_crash;       // [n], null: a base without crash rounds
+  const int32_t* base_init;  // [n]
+  uint64_t* part;            // CRASH: the base's crash-round deliveries [n][W]
+  // [units + 2]: exclusive prefix of the candidates each unit of the level contributes (a unit: the
+  // tail, a round, a set, a crash edit), pre[units] their sum, pre[units + 1] the level's total
+  // (the sum, or LINK's capped count)
+  uint32_t* pre;
+  ShrinkEdit* edit;          // [count]: the edits of candidates [first, first + count)
+  uint64_t* ho;              // destination sets [count][R][n][W]
+  int32_t* crash;            // destination crash rounds [count][n] (nullable)
+  int32_t* init;             // destination initial values [count][n] (nullable)
+  uint64_t* partial;         // CRASH: destination delivery sets [count][n][W] (nullable)
+  uint64_t first, count;
+  int n, R, W;
+  int32_t level;  // enum psg_shrink_level
+  uint32_t arg;
+  uint32_t units;
+};
 // a population's initial values: {1..V}; BenOr's {0, 1} coin bit; TwoPhaseCommit's vote (tpc_vote);
 // LatticeAgreement's set (lattice_init)
 enum { POP_INIT_VALUE = 0, POP_INIT_COIN = 1, POP_INIT_VOTE = 2, POP_INIT_SET = 3 };

@@ -10,6 +10,7 @@ struct KArgs;
 struct VmArgs;
 struct PopArgs;
 struct LiveArgs;
+struct ShrinkArgs;
 
 // Runtime W (mask words, 1..4) -> compile-time constant: f(std::integral_constant<int, W>) for a
 // generic callable f, `bad` outside that range.
@@ -61,6 +62,18 @@ hipError_t launch_population(const PopArgs& a, hipStream_t s);
 hipError_t launch_population_live(const PopArgs& a, hipStream_t s);
 hipError_t launch_population_crash(const PopArgs& a, hipStream_t s);
 hipError_t launch_live_predicate(const LiveArgs& a, hipStream_t s);
+// genome -> HO sets alone: a.ho [count][R][n][W] from a.crash, a.partial (pop_crash_ho_kernel)
+hipError_t launch_crash_ho(const PopArgs& a, hipStream_t s);
+// shrinking on the device (psg_shrink.hip): the level's prefix and total over the base; the edits
+// of candidates [first, first + count); the candidates' sets (or, ho = base and count = 1, the base
+// edited in place); their initial values, crash rounds and (CRASH) delivery sets; the base's
+// crash-round deliveries; links of every loaded instance
+hipError_t launch_shrink_scan(const ShrinkArgs& a, hipStream_t s);
+hipError_t launch_shrink_edits(const ShrinkArgs& a, hipStream_t s);
+hipError_t launch_shrink_fill(const ShrinkArgs& a, hipStream_t s);
+hipError_t launch_shrink_rows(const ShrinkArgs& a, hipStream_t s);
+hipError_t launch_shrink_part(const ShrinkArgs& a, hipStream_t s);
+hipError_t launch_links(const uint64_t* ho, uint32_t* links, uint64_t count, int n, int R, int W, hipStream_t s);
 hipError_t launch_spec_vm(const VmArgs& a, int grid, hipStream_t s);
 hipError_t launch_gen_init(uint64_t inst_begin, uint64_t count, int n, int alg, int V, uint64_t seed, int32_t* out,
                            hipStream_t s);

@@ -52,11 +52,6 @@ PSG_DEV U4 pop_draw(const PopArgs& a, uint64_t slot, uint32_t c2, uint32_t c3) {
   return philox10((uint32_t)slot, a.gen, c2, c3, (uint32_t)a.seed, (uint32_t)(a.seed >> 32));
 }
 
-PSG_DEV uint64_t full_word(int n, int w) {
-  const int b = n - 64 * w;
-  return b >= 64 ? ~0ull : (b <= 0 ? 0ull : ((1ull << b) - 1ull));
-}
-
 __global__ void __launch_bounds__(256) pop_links_kernel(PopArgs a) {
   const uint64_t sets = a.count * (uint64_t)a.R * (uint64_t)a.n;
   for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < sets; e += (uint64_t)gridDim.x * blockDim.x) {
@@ -466,6 +461,14 @@ hipError_t launch_population_crash(const PopArgs& a, hipStream_t s) {
     if (a.op && a.flips) hipLaunchKernelGGL(pop_partial_flip_kernel, dim3(grid(a.count * a.flips)), dim3(256), 0, s, a);
     hipLaunchKernelGGL(pop_crash_ho_kernel<W>, dim3(wave_grid(a.count)), dim3(256), 0, s, a);
     hipLaunchKernelGGL(pop_init_kernel, dim3(grid(a.count * (uint64_t)a.n)), dim3(256), 0, s, a);
+    return hipGetLastError();
+  });
+}
+
+hipError_t launch_crash_ho(const PopArgs& a, hipStream_t s) {
+  if (a.count == 0) return hipSuccess;
+  return with_w<hipError_t>(a.W, hipErrorInvalidValue, [&](auto w) {
+    hipLaunchKernelGGL(pop_crash_ho_kernel<decltype(w)::value>, dim3(wave_grid(a.count)), dim3(256), 0, s, a);
     return hipGetLastError();
   });
 }

@@ -28,6 +28,8 @@ EXPORTED_SYMBOLS = [
     "psg_population_fresh", "psg_population_next", "psg_population_read", "psg_population_fresh_model",
     "psg_population_next_model", "psg_population_read_crash", "psg_population_live", "psg_spec_from_text",
     "psg_spec_release",
+    "psg_population_links", "psg_shrink_begin", "psg_shrink_count", "psg_shrink_load", "psg_shrink_adopt",
+    "psg_shrink_read",
     "psg_spec_compile_native", "psg_spec_native_source", "psg_selftest_bitset", "psg_spec_rewrite_text",
     "psg_spec_set_options", "psg_pack_width",
 ]
@@ -101,6 +103,12 @@ def load():
                                           C.POINTER(C.c_int32), C.c_int32]
         L.psg_spec_set_options.argtypes = [C.c_char_p]
         L.psg_pack_width.argtypes = [C.c_int32, C.c_int32]
+        L.psg_population_links.argtypes = [C.c_void_p, C.c_void_p]
+        L.psg_shrink_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.psg_shrink_count.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.POINTER(C.c_uint64)]
+        L.psg_shrink_load.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64]
+        L.psg_shrink_adopt.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.c_uint64]
+        L.psg_shrink_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     except AttributeError:
         pass
     L.psg_spec_release.argtypes = [C.POINTER(abi.SpecProgram)]
@@ -348,6 +356,58 @@ class Context:
         live = np.zeros((getattr(self, "_ho_count", 0), self.cfg.rounds), np.uint8)
         self._check(load().psg_population_live(self._h, live_kind, phase, coord, live.ctypes.data_as(C.c_void_p)))
         return live
+
+    def population_links(self):
+        """psg_population_links: uint32 [count], the links present (bits < n) in every instance of
+        the loaded explicit schedule."""
+        import numpy as np
+        links = np.zeros(getattr(self, "_ho_count", 0), np.uint32)
+        self._check(load().psg_population_links(self._h, links.ctypes.data_as(C.c_void_p)))
+        return links
+
+    def shrink_begin(self, ho, crash, init):
+        """psg_shrink_begin: the shrink base, ho uint64 [R][n][W], crash int32 [n] or None, init int32 [n]."""
+        import numpy as np
+        W = (self.cfg.n + 63) // 64
+        ho = np.ascontiguousarray(ho, dtype=np.uint64)
+        init = np.ascontiguousarray(init, dtype=np.int32)
+        if ho.size != self.cfg.rounds * self.cfg.n * W or init.size != self.cfg.n:
+            raise ValueError("ho must be [rounds][n][W] uint64 and init [n] int32")
+        cr = None
+        if crash is not None:
+            cr = np.ascontiguousarray(crash, dtype=np.int32)
+            if cr.size != self.cfg.n:
+                raise ValueError("crash must be [n] int32")
+        self._check(load().psg_shrink_begin(self._h, ho.ctypes.data_as(C.c_void_p),
+                                            None if cr is None else cr.ctypes.data_as(C.c_void_p),
+                                            init.ctypes.data_as(C.c_void_p)))
+        self._sh_crash = cr is not None
+
+    def shrink_count(self, level, arg=0):
+        """psg_shrink_count: the candidates of the level (abi.PSG_SHRINK_*) over the base."""
+        total = C.c_uint64()
+        self._check(load().psg_shrink_count(self._h, level, arg, C.byref(total)))
+        return int(total.value)
+
+    def shrink_load(self, level, arg, first, count, inst_begin):
+        """psg_shrink_load: candidates [first, first + count) of the level become the loaded explicit
+        schedule and staged inputs of instances [inst_begin, inst_begin + count)."""
+        self._check(load().psg_shrink_load(self._h, level, arg, first, count, inst_begin))
+        self._ho_count = count
+
+    def shrink_adopt(self, level, arg, j):
+        """psg_shrink_adopt: the base becomes candidate j of the level."""
+        self._check(load().psg_shrink_adopt(self._h, level, arg, j))
+
+    def shrink_read(self):
+        """psg_shrink_read: the base, (ho uint64 [R][n][W], crash int32 [n] or None)."""
+        import numpy as np
+        W = (self.cfg.n + 63) // 64
+        ho = np.zeros((self.cfg.rounds, self.cfg.n, W), np.uint64)
+        cr = np.zeros(self.cfg.n, np.int32) if getattr(self, "_sh_crash", False) else None
+        self._check(load().psg_shrink_read(self._h, ho.ctypes.data_as(C.c_void_p),
+                                           None if cr is None else cr.ctypes.data_as(C.c_void_p)))
+        return ho, cr
 
     def close(self):
         if getattr(self, "_h", None):

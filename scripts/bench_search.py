@@ -14,6 +14,11 @@ Rows (one JSON line each, then a JSON list in --out):
     (psg_population_*_model).
 --ab-models N measures those two rows only: one warm-up search per row and path, then N passes
 alternating the host-generator and the device-model path.
+--ab-shrink N measures the shrink step only: per row (the OTR safety mutant at n=64, R=8, population
+4096; an OTR liveness search with one good round at n=64, R=20) one counterexample found with
+shrink=False, one warm-up of each path, then N passes alternating Adversary.shrink and
+Adversary.shrink_device on that counterexample; per pass seconds, steps, candidates evaluated and
+whether the two results are identical.
 """
 import argparse
 import json
@@ -60,8 +65,64 @@ def model_rows(population, generations, device_models, **extra):
     return out
 
 
+def same_counterexample(a, b):
+    return ((a.ho == b.ho).all() and (a.crash is None) == (b.crash is None)
+            and (a.crash is None or (a.crash == b.crash).all()) and a.check_point == b.check_point
+            and a.violated == b.violated and a.omitted_links == b.omitted_links
+            and bytes(a.summary.tobytes()) == bytes(b.summary.tobytes()))
+
+
+def shrink_rows(name, alg, n, R, passes, max_steps, population, generations=60, **kw):
+    """One counterexample found with shrink=False, then `passes` passes alternating Adversary.shrink
+    (the host builds and uploads every candidate) and Adversary.shrink_device (psg_shrink_*) on it,
+    after one warm-up of each. Per pass: seconds, steps, candidates evaluated, identical results.
+    (Liveness rows: the device path also evaluates the candidates with too few live rounds, which the
+    host drops before evaluating, so its count can be the larger one.)"""
+    rows = []
+    with A.Adversary(alg, n, R, population=population, seed=7, **kw) as adv:
+        res = adv.search(generations=generations, want=1, shrink=False)
+        if not res.counterexamples:
+            raise SystemExit(f"{name}: no counterexample in {res.schedules_evaluated} schedules")
+        c = res.counterexamples[0]
+        counted = {"batches": 0, "candidates": 0}
+        still_bad = adv._still_bad
+
+        def counting(cur, hos, crashes):
+            counted["batches"] += 1
+            counted["candidates"] += int(hos.shape[0])
+            return still_bad(cur, hos, crashes)
+
+        adv._still_bad = counting
+
+        def one(path, k):
+            counted.update(batches=0, candidates=0)
+            t0 = time.perf_counter()
+            out = adv.shrink(c, max_steps) if path == "host" else adv.shrink_device(c, max_steps)
+            secs = time.perf_counter() - t0
+            stats = dict(counted) if path == "host" else adv.shrink_stats
+            return out, {"row": name, "path": path, "pass": k, "n": n, "rounds": R, "population": population,
+                         "max_steps": max_steps, "seconds": round(secs, 4), "batches": stats["batches"],
+                         "steps": stats.get("steps"), "candidates": stats["candidates"],
+                         "omitted_links_before": int(c.omitted_links), "omitted_links_after": int(out.omitted_links)}
+
+        one("host", -1)
+        one("device", -1)
+        for k in range(passes):
+            host, hrow = one("host", k)
+            dev, drow = one("device", k)
+            hrow["identical"] = drow["identical"] = bool(same_counterexample(host, dev))
+            for r in (hrow, drow):
+                print(json.dumps(r), flush=True)
+            rows += [hrow, drow]
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--ab-shrink", type=int, default=0, metavar="N",
+                    help="only the shrink comparison: per row one counterexample, a warm-up, then N passes "
+                         "alternating shrink() and shrink_device() on it")
+    ap.add_argument("--max-steps", type=int, default=64, help="--ab-shrink: the step budget of both paths")
     ap.add_argument("--device-models", action="store_true",
                     help="crash-stop and liveness searches generate their populations on the GPU")
     ap.add_argument("--ab-models", type=int, default=0, metavar="N",
@@ -70,6 +131,16 @@ def main():
     ap.add_argument("--population", type=int, default=32768)
     ap.add_argument("--generations", type=int, default=8)
     a = ap.parse_args()
+    if a.ab_shrink:
+        rows = shrink_rows("mut_otr_n64_safety", psync.OTR(variant=1), 64, 8, a.ab_shrink, a.max_steps, 4096,
+                           targets=["Safety"])
+        # one good round is not enough for OTR: found in the first generation
+        rows += shrink_rows("live_otr_n64_one_good_round", psync.OTR(), 64, 20, a.ab_shrink, a.max_steps, a.population,
+                            mode="liveness", live_rounds=1, device_models=True)
+        if a.out:
+            with open(a.out, "w") as f:
+                json.dump(rows, f, indent=1)
+        return
     if a.ab_models:
         rows = []
         for dm in (False, True):

@@ -1,0 +1,157 @@
+"""Shrinking on the device, the CPU side: the restatement of the candidate lists (tests/shrink_ref.py,
+what psg_shrink_* is tested against on the GPU) is pinned to the batches Adversary.shrink really
+evaluates; the device_shrink switch falls back to shrink() without the GPU evaluator; the enum and
+the exports of the C ABI."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from round_amd import abi, adversary as A, lib, psync, schedules as S
+
+from oracle_eval import OracleEvaluator
+from shrink_ref import candidates, same_cex
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LEVELS = (abi.PSG_SHRINK_TAIL, abi.PSG_SHRINK_ROUND, abi.PSG_SHRINK_SET, abi.PSG_SHRINK_LINK, abi.PSG_SHRINK_CRASH)
+NEW_SYMBOLS = ("psg_shrink_begin", "psg_shrink_count", "psg_shrink_load", "psg_shrink_adopt", "psg_shrink_read",
+               "psg_population_links")
+
+
+class Recorder:
+    """An evaluator that keeps every batch it is handed."""
+
+    def __init__(self, inner):
+        self.inner = inner
+        self.calls = []
+
+    def __call__(self, inst_begin, ho, crash, init):
+        self.calls.append((np.array(ho), None if crash is None else np.array(crash), np.array(init), inst_begin))
+        return self.inner(inst_begin, ho, crash, init)
+
+
+#        name, algorithm, n, R, population, values, mode, keywords
+CASES = [
+    ("otr-n8", psync.OTR(variant=1), 8, 6, 512, 3, "safety", dict(targets=["Agreement"])),
+    # population 8: at 64, 32 and 16 the tail step leaves fewer missing links than the cap 4 * population,
+    # here the LINK batches (33..40 candidates) are cut by the cap of 32
+    ("otr-n16-cap", psync.OTR(variant=1), 16, 6, 8, 2, "safety", {}),
+    ("kses-n8", psync.KSetEarlyStopping(t=3, k=2, variant=1), 8, 5, 512, 3, "safety", {}),
+    ("otr-live-n8", psync.OTR(), 8, 6, 512, 3, "liveness", dict(live_rounds=1)),
+]
+
+
+@pytest.mark.parametrize("name,alg,n,R,P,V,mode,kw", CASES, ids=[c[0] for c in CASES])
+def test_restatement_is_what_shrink_evaluates(name, alg, n, R, P, V, mode, kw, oracle_mod):
+    rec = Recorder(OracleEvaluator(alg, n, R, value_range=V))
+    adv = A.Adversary(alg, n, R, mode=mode, population=P, values=V, evaluator=rec, seed=5, **kw)
+    res = adv.search(generations=40, want=1, shrink=False)
+    assert res.counterexamples, name
+    c0 = res.counterexamples[0]
+    steps = []  # (base ho, base crash, check point of the base, first recorded call, level) of the step
+    still_bad = adv._still_bad
+    names = {"round": abi.PSG_SHRINK_ROUND, "set": abi.PSG_SHRINK_SET, "link": abi.PSG_SHRINK_LINK}
+
+    def marking(c, hos, crashes):
+        # the level is shrink()'s own: the loop variable of the frame that called accept() (before
+        # the loop: the tail step; the crash family has one level)
+        loop = sys._getframe(2)
+        assert loop.f_code is A.Adversary.shrink.__code__
+        level = abi.PSG_SHRINK_CRASH if adv.model.family == "crash" else \
+            names[loop.f_locals["level"]] if "level" in loop.f_locals else abi.PSG_SHRINK_TAIL
+        steps.append((c.ho.copy(), None if c.crash is None else c.crash.copy(), c.check_point, len(rec.calls), level))
+        return still_bad(c, hos, crashes)
+
+    adv._still_bad = marking
+    rec.calls.clear()
+    c1 = adv.shrink(c0)
+    assert steps and not same_cex(c0, c1), f"{name}: shrink() left the counterexample unchanged"
+    bounds = [s[3] for s in steps] + [len(rec.calls)]
+    level_at, truncated = [], 0
+    for (ho, crash, cp, a, level), b in zip(steps, bounds[1:]):
+        got_ho = np.concatenate([x[0] for x in rec.calls[a:b]])  # (chunks of `population`)
+        got_cr = None if crash is None else np.concatenate([x[1] for x in rec.calls[a:b]])
+        assert all((x[2] == c0.init).all() and x[3] == c0.inst_id for x in rec.calls[a:b])
+        arg = {abi.PSG_SHRINK_TAIL: cp, abi.PSG_SHRINK_LINK: 4 * P}.get(level, 0)
+        want_ho, want_cr = candidates(ho, crash, level, arg, n, R, adv.self_bit)
+        if mode == "liveness":  # the host drops candidates with too few live rounds before it evaluates
+            want_ho = want_ho[adv._live_count(want_ho) >= adv.live_rounds]
+        assert want_ho.shape == got_ho.shape and (want_ho == got_ho).all(), (name, len(level_at), level)
+        assert crash is None or (want_cr == got_cr).all()
+        if level == abi.PSG_SHRINK_LINK:
+            truncated += len(candidates(ho, crash, level, 0, n, R)[0]) > len(want_ho) > 4 * P
+        level_at.append(level)
+    assert level_at == sorted(level_at) and (level_at[0] == abi.PSG_SHRINK_TAIL) == (mode == "safety" and
+                                                                                    adv.model.family != "crash")
+    print(f"{name}: levels {level_at}, omitted links {c0.omitted_links} -> {c1.omitted_links}")
+    if name == "otr-n16-cap":
+        assert truncated >= 1, "no LINK batch was cut by the cap 4 * population"
+    if name == "kses-n8":
+        assert (c1.crash >= 0).sum() < (c0.crash >= 0).sum()  # a crash step was accepted
+    if adv.model.family == "omission":
+        assert abi.PSG_SHRINK_LINK in level_at
+
+
+def test_link_cap_rule():
+    """The cap is tested after each set: the list ends with the first set that brings it above."""
+    n, R = 5, 2
+    ho = np.zeros((R, n, 1), np.uint64)
+    ho[:, :, 0] = [[0b00001, 0b11111, 0b00111, 0b01010, 0b10000], [0b11111, 0b01111, 0, 0b11111, 0b11110]]
+    missing = [4, 0, 2, 3, 4, 0, 1, 5, 0, 1]
+    assert len(candidates(ho, None, abi.PSG_SHRINK_LINK, 0, n, R)[0]) == sum(missing)
+    assert len(candidates(ho, None, abi.PSG_SHRINK_LINK, 1, n, R)[0]) == 4
+    assert len(candidates(ho, None, abi.PSG_SHRINK_LINK, 4, n, R)[0]) == 6   # 4 is not above 4
+    assert len(candidates(ho, None, abi.PSG_SHRINK_LINK, 7, n, R)[0]) == 9   # the cap falls inside a set
+    assert len(candidates(ho, None, abi.PSG_SHRINK_LINK, 100, n, R)[0]) == sum(missing)
+
+
+def test_device_shrink_falls_back_without_the_gpu_evaluator(oracle_mod):
+    alg, n, R = psync.OTR(variant=1), 8, 6
+    out = []
+    for flag in (False, True):
+        adv = A.Adversary(alg, n, R, targets=["Agreement"], population=512, evaluator=OracleEvaluator(alg, n, R),
+                          seed=5, device_shrink=flag)
+        assert adv.device_shrink is flag and adv.device_shrink_available() is False
+        out.append(adv.search(generations=40, want=2).counterexamples)
+        with pytest.raises(ValueError):
+            adv.shrink_device(out[-1][0])
+    assert out[0] and len(out[0]) == len(out[1])
+    assert all(same_cex(a, b) for a, b in zip(*out))
+    assert A.Adversary(alg, n, R, evaluator=OracleEvaluator(alg, n, R)).device_shrink is False  # off by default
+
+
+PROBE = r"""
+#include <stdio.h>
+#include "psg.h"
+int main(void) {
+  printf("%d %d %d %d %d\n", (int)PSG_SHRINK_TAIL, (int)PSG_SHRINK_ROUND, (int)PSG_SHRINK_SET, (int)PSG_SHRINK_LINK,
+         (int)PSG_SHRINK_CRASH);
+  return 0;
+}
+"""
+
+
+def test_shrink_levels_match_header(tmp_path):
+    src = tmp_path / "probe.c"
+    src.write_text(PROBE)
+    exe = tmp_path / "probe"
+    subprocess.check_call(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    got = [int(v) for v in subprocess.check_output([str(exe)], text=True).split()]
+    assert got == list(LEVELS) == [0, 1, 2, 3, 4]
+
+
+def test_shrink_symbols_exported():
+    L = lib.load()
+    out = subprocess.check_output(["nm", "-D", "--defined-only", lib.LIB_PATH], text=True)
+    exported = {line.split()[-1] for line in out.splitlines() if " T " in line}
+    for name in NEW_SYMBOLS:
+        assert name in exported and name in lib.EXPORTED_SYMBOLS and hasattr(L, name), name
+    # a null context is refused before anything is touched
+    assert L.psg_shrink_begin(None, None, None, None) == abi.PSG_EINVAL
+    assert L.psg_shrink_count(None, 0, 0, None) == abi.PSG_EINVAL
+    assert L.psg_shrink_load(None, 0, 0, 0, 0, 0) == abi.PSG_EINVAL
+    assert L.psg_shrink_adopt(None, 0, 0, 0) == abi.PSG_EINVAL
+    assert L.psg_shrink_read(None, None, None) == abi.PSG_EINVAL
+    assert L.psg_population_links(None, None) == abi.PSG_EINVAL
