@@ -587,6 +587,40 @@ int psg_selftest_map_head(int32_t device, const uint64_t* sets, int32_t count, i
  * 6 size -> out. Results of get / size are written to out[0..n_out) in order. */
 int psg_selftest_bitset(int32_t device, int32_t W, const int32_t* ops, int32_t n_ops, int32_t* out, int32_t n_out);
 
+/* Self-test hooks (tests only) of the EpsilonConsensus kernel's building blocks: each runs one of
+ * them on caller data on device `device`, through the functions the round kernel calls. At most
+ * 2^20 items or cases per call; 0 is allowed and touches nothing.
+ *
+ * f64: one lane per x. out_f64 [3][count]: the kernel's log, the device library's log, and the
+ * double rebuilt from the Double.compare key; out_key [count]: that key (signed order; -0.0 < 0.0,
+ * one canonical NaN above +inf); out_i32 [3][count]: Java's (int) x, (int) ceil(x), and the 32-bit
+ * fold of x's bits the digests use.
+ * maxr: out [count] = (int) ceil(log(q) / log(c)) as round 0 forms maxR (Epsilon.scala:36). */
+int psg_selftest_eps_f64(int32_t device, const double* x, int32_t count, double* out_f64, int64_t* out_key,
+                         int32_t* out_i32);
+int psg_selftest_eps_maxr(int32_t device, const double* q, const double* c, int32_t count, int32_t* out);
+/* sort: one wave per case; x [cases][64], n [cases] in 1..64 (lanes >= n are padding). out_x, out_pid
+ * [cases][64]: the value and process at each sorted position (Double.compare order, ties by pid;
+ * positions >= n hold the padding lanes); out_fallback [cases]: 1 when the (key, pid) network ran
+ * after the one-word sort. network 0: the round kernel's sequence; 1: the (key, pid) network alone
+ * (out_fallback 0). */
+int psg_selftest_eps_sort(int32_t device, int32_t network, const double* x, const int32_t* n, int32_t cases,
+                          double* out_x, int32_t* out_pid, int32_t* out_fallback);
+/* transpose: rows, out [cases][64]: the 64 x 64 bit-matrix transpose, out[c][j] bit i = rows[c][i] bit j.
+ * select: masks [count], each non-zero; out [count][64]: the position of the j-th set bit for
+ * j < popcount, then -1.
+ * members: U, out [cases][64], spid [cases][64] in 0..63: out[c][p] bit t = U[c][p] bit spid[c][t]. */
+int psg_selftest_eps_transpose(int32_t device, const uint64_t* rows, int32_t cases, uint64_t* out);
+int psg_selftest_eps_select(int32_t device, const uint64_t* masks, int32_t count, int32_t* out);
+int psg_selftest_eps_members(int32_t device, const uint64_t* U, const int32_t* spid, int32_t cases, uint64_t* out);
+/* reduce: the group reductions of a W-wave group of n processes (W = 1..4, n <= 64W). v, in
+ * [cases][3][64W]: three data sets per case, every reduction called on them back to back.
+ * out [cases][9][W]: per wave (as its lane 0 holds them) the minimum over the processes with `in`
+ * of sets 0, 1, 2 (INT64_MAX when none), the maximum likewise (INT64_MIN), then the sum mod 2^64
+ * over all n processes (no flag). */
+int psg_selftest_eps_reduce(int32_t device, int32_t W, int32_t n, const int64_t* v, const uint8_t* in, int32_t cases,
+                            int64_t* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -505,6 +505,18 @@ __global__ void bitset_selftest_kernel(const int32_t* ops, int n_ops, int32_t* o
   }
 }
 
+// psg_selftest_eps_*: a self-test's scratch buffer filled from host data, and read back
+constexpr int32_t kEpsSelftestMax = 1 << 20;  // items or cases per call
+template <class T>
+static int st_up(DevBuf<T>& d, const T* h, uint64_t count) {
+  if (d.grow(count) != hipSuccess) return PSG_ENOMEM;
+  return hipMemcpy(d, h, sizeof(T) * count, hipMemcpyHostToDevice) == hipSuccess ? PSG_OK : PSG_EIO;
+}
+template <class T>
+static int st_down(T* h, const DevBuf<T>& d, uint64_t count) {
+  return hipMemcpy(h, d, sizeof(T) * count, hipMemcpyDeviceToHost) == hipSuccess ? PSG_OK : PSG_EIO;
+}
+
 extern "C" {
 
 int psg_config_default(psg_config* cfg, int32_t alg, int32_t n) {
@@ -559,7 +571,7 @@ int psg_alg_from_class(const char* name) {
 
 const char* psg_create_error(void) { return g_create_err.c_str(); }
 
-// Both selftests run on the null stream of `device`; their scratch buffers free themselves.
+// The selftests run on the null stream of `device`; their scratch buffers free themselves.
 static int selftest_device(int32_t device) {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return PSG_ENODEV;
@@ -598,6 +610,114 @@ int psg_selftest_bitset(int32_t device, int32_t W, const int32_t* ops, int32_t n
   if (e != hipSuccess || (n_out > 0 && hipMemcpy(out, d_out, sizeof(int32_t) * n_out, hipMemcpyDeviceToHost) != hipSuccess))
     return PSG_EIO;
   return PSG_OK;
+}
+
+// psg_selftest_eps_*: caller data up (st_up), one kernel of psg_epsilon.hip, results down (st_down)
+int psg_selftest_eps_f64(int32_t device, const double* x, int32_t count, double* out_f64, int64_t* out_key, int32_t* out_i32) {
+  if (!x || !out_f64 || !out_key || !out_i32 || count < 0 || count > kEpsSelftestMax) return PSG_EINVAL;
+  if (count == 0) return PSG_OK;
+  if (int rc = selftest_device(device)) return rc;
+  const uint64_t c = (uint64_t)count;
+  DevBuf<double> d_x, d_f;
+  DevBuf<int64_t> d_k;
+  DevBuf<int32_t> d_i;
+  if (int rc = st_up(d_x, x, c)) return rc;
+  if (d_f.grow(3 * c) != hipSuccess || d_k.grow(c) != hipSuccess || d_i.grow(3 * c) != hipSuccess) return PSG_ENOMEM;
+  if (launch_eps_selftest_f64(d_x, count, d_f, d_k, d_i, nullptr) != hipSuccess) return PSG_EIO;
+  if (int rc = st_down(out_f64, d_f, 3 * c)) return rc;
+  if (int rc = st_down(out_key, d_k, c)) return rc;
+  return st_down(out_i32, d_i, 3 * c);
+}
+
+int psg_selftest_eps_maxr(int32_t device, const double* q, const double* c, int32_t count, int32_t* out) {
+  if (!q || !c || !out || count < 0 || count > kEpsSelftestMax) return PSG_EINVAL;
+  if (count == 0) return PSG_OK;
+  if (int rc = selftest_device(device)) return rc;
+  DevBuf<double> d_q, d_c;
+  DevBuf<int32_t> d_o;
+  if (int rc = st_up(d_q, q, (uint64_t)count)) return rc;
+  if (int rc = st_up(d_c, c, (uint64_t)count)) return rc;
+  if (d_o.grow((uint64_t)count) != hipSuccess) return PSG_ENOMEM;
+  if (launch_eps_selftest_maxr(d_q, d_c, count, d_o, nullptr) != hipSuccess) return PSG_EIO;
+  return st_down(out, d_o, (uint64_t)count);
+}
+
+int psg_selftest_eps_sort(int32_t device, int32_t network, const double* x, const int32_t* n, int32_t cases, double* out_x,
+                          int32_t* out_pid, int32_t* out_fallback) {
+  if (!x || !n || !out_x || !out_pid || !out_fallback || cases < 0 || cases > kEpsSelftestMax) return PSG_EINVAL;
+  if (network != 0 && network != 1) return PSG_EINVAL;
+  for (int32_t i = 0; i < cases; ++i)
+    if (n[i] < 1 || n[i] > 64) return PSG_EINVAL;
+  if (cases == 0) return PSG_OK;
+  if (int rc = selftest_device(device)) return rc;
+  const uint64_t c = (uint64_t)cases;
+  DevBuf<double> d_x, d_ox;
+  DevBuf<int32_t> d_n, d_pid, d_fell;
+  if (int rc = st_up(d_x, x, 64 * c)) return rc;
+  if (int rc = st_up(d_n, n, c)) return rc;
+  if (d_ox.grow(64 * c) != hipSuccess || d_pid.grow(64 * c) != hipSuccess || d_fell.grow(c) != hipSuccess) return PSG_ENOMEM;
+  if (launch_eps_selftest_sort(network, d_x, d_n, cases, d_ox, d_pid, d_fell, nullptr) != hipSuccess) return PSG_EIO;
+  if (int rc = st_down(out_x, d_ox, 64 * c)) return rc;
+  if (int rc = st_down(out_pid, d_pid, 64 * c)) return rc;
+  return st_down(out_fallback, d_fell, c);
+}
+
+int psg_selftest_eps_transpose(int32_t device, const uint64_t* rows, int32_t cases, uint64_t* out) {
+  if (!rows || !out || cases < 0 || cases > kEpsSelftestMax) return PSG_EINVAL;
+  if (cases == 0) return PSG_OK;
+  if (int rc = selftest_device(device)) return rc;
+  const uint64_t c = (uint64_t)cases;
+  DevBuf<uint64_t> d_in, d_out;
+  if (int rc = st_up(d_in, rows, 64 * c)) return rc;
+  if (d_out.grow(64 * c) != hipSuccess) return PSG_ENOMEM;
+  if (launch_eps_selftest_transpose(d_in, cases, d_out, nullptr) != hipSuccess) return PSG_EIO;
+  return st_down(out, d_out, 64 * c);
+}
+
+int psg_selftest_eps_select(int32_t device, const uint64_t* masks, int32_t count, int32_t* out) {
+  if (!masks || !out || count < 0 || count > kEpsSelftestMax) return PSG_EINVAL;
+  for (int32_t i = 0; i < count; ++i)
+    if (masks[i] == 0) return PSG_EINVAL;
+  if (count == 0) return PSG_OK;
+  if (int rc = selftest_device(device)) return rc;
+  const uint64_t c = (uint64_t)count;
+  DevBuf<uint64_t> d_m;
+  DevBuf<int32_t> d_out;
+  if (int rc = st_up(d_m, masks, c)) return rc;
+  if (d_out.grow(64 * c) != hipSuccess) return PSG_ENOMEM;
+  if (launch_eps_selftest_select(d_m, count, d_out, nullptr) != hipSuccess) return PSG_EIO;
+  return st_down(out, d_out, 64 * c);
+}
+
+int psg_selftest_eps_members(int32_t device, const uint64_t* U, const int32_t* spid, int32_t cases, uint64_t* out) {
+  if (!U || !spid || !out || cases < 0 || cases > kEpsSelftestMax) return PSG_EINVAL;
+  for (int64_t i = 0; i < 64 * (int64_t)cases; ++i)
+    if (spid[i] < 0 || spid[i] > 63) return PSG_EINVAL;
+  if (cases == 0) return PSG_OK;
+  if (int rc = selftest_device(device)) return rc;
+  const uint64_t c = (uint64_t)cases;
+  DevBuf<uint64_t> d_u, d_out;
+  DevBuf<int32_t> d_p;
+  if (int rc = st_up(d_u, U, 64 * c)) return rc;
+  if (int rc = st_up(d_p, spid, 64 * c)) return rc;
+  if (d_out.grow(64 * c) != hipSuccess) return PSG_ENOMEM;
+  if (launch_eps_selftest_members(d_u, d_p, cases, d_out, nullptr) != hipSuccess) return PSG_EIO;
+  return st_down(out, d_out, 64 * c);
+}
+
+int psg_selftest_eps_reduce(int32_t device, int32_t W, int32_t n, const int64_t* v, const uint8_t* in, int32_t cases,
+                            int64_t* out) {
+  if (!v || !in || !out || W < 1 || W > 4 || n < 1 || n > 64 * W || cases < 0 || cases > kEpsSelftestMax) return PSG_EINVAL;
+  if (cases == 0) return PSG_OK;
+  if (int rc = selftest_device(device)) return rc;
+  const uint64_t c = (uint64_t)cases, per = 3ull * 64 * (uint64_t)W;
+  DevBuf<int64_t> d_v, d_out;
+  DevBuf<uint8_t> d_in;
+  if (int rc = st_up(d_v, v, per * c)) return rc;
+  if (int rc = st_up(d_in, in, per * c)) return rc;
+  if (d_out.grow(9ull * (uint64_t)W * c) != hipSuccess) return PSG_ENOMEM;
+  if (launch_eps_selftest_reduce(W, n, d_v, d_in, cases, d_out, nullptr) != hipSuccess) return PSG_EIO;
+  return st_down(out, d_out, 9ull * (uint64_t)W * c);
 }
 
 static int validate(const psg_config* cfg, std::string& m) {

@@ -41,6 +41,7 @@ PSG_DEV int32_t d2i(double d) {
 // loop-invariant: the compiler hoists them out of the instance loop into VGPR pairs that stay live
 // across every round and spill (96 B of scratch at 6 waves/SIMD, round 5). Here each literal passes
 // an opaque copy at its use, so it is materialized where log runs (once per instance, maxR).
+// (Bit equality with the library's log() on the device: psg_selftest_eps_f64, tests/test_gpu_eps_primitives.py.)
 template <uint64_t BITS>
 PSG_DEV double lit64() {  // the double with these bits, materialized here (two v_mov_b32 in asm)
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -532,6 +533,215 @@ hipError_t launch_epsilon(const KArgs& a, int W, int grid, hipStream_t s) {
 
 const void* epsilon_kernel_ptr(int W) {
   return with_w(W, (const void*)nullptr, [](auto w) { return (const void*)epsilon_kernel<w(), false>; });
+}
+
+// ---------------------------------------------------------------- self-tests (psg_selftest_eps_*)
+// Each kernel runs one building block of epsilon_kernel on caller data, through the functions the
+// round kernel calls. The wave-wide ones take one wave per case, four cases per block.
+//
+// Four short sequences stand inline in epsilon_kernel and are restated here, statement for
+// statement: the W = 1 sort with its adjacent-key test, the sel8 table loop, the Us transposes
+// and the maxR expression. As shared functions they changed the round kernel's code (register
+// allocation, a v_and_or_b32 split in two in the sort) and the W2 row measured 9.54-9.55 ms
+// against 9.48-9.50 ms in five alternating pairs, so the kernel keeps its text; the end-to-end
+// and parity tests tie the inline text to these copies. Change both together.
+
+// epsilon_kernel's W = 1 sort: every process's current x in total order, ties by pid. Lane t
+// returns the value at sorted position t and gets its process in spid_r; padding lanes sort last.
+// `fell`: the (key, pid) network ran.
+PSG_DEV double wave_sort_values(Grp<1>& g, int n, double x, int32_t& spid_r, bool& fell) {
+  const int64_t key = total_key(x);
+  // padding lanes sort last: no valid key reaches INT64_MAX's top 58 bits (NaN's is 0x7ff8 << 48)
+  int64_t c = ((g.valid ? key : INT64_MAX) & ~(int64_t)63) | g.lane;
+  wave_sort_packed(c, g.lane);
+  spid_r = (int32_t)(c & 63);
+  double xs = __shfl(x, spid_r);
+  // position t's full key against position t - 1's (DPP wave_shr:1, no LDS round trip)
+  const int64_t ks = total_key(xs);
+  const int64_t kp = (int64_t)((uint64_t)(uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)ks, 0x138, 0xF, 0xF, false) |
+                               ((uint64_t)(uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(ks >> 32), 0x138, 0xF, 0xF, false) << 32));
+  fell = g.any(g.lane >= 1 && g.lane < n && kp > ks);
+  if (fell) {  // rare: keys within 64 ulp out of pid order
+    int64_t skey = g.valid ? key : INT64_MAX;
+    spid_r = g.lane;
+    wave_sort_key_pid(skey, spid_r, g.lane);
+    xs = __shfl(x, spid_r);
+  }
+  return xs;
+}
+
+// W = 1: Us(p) bit t = [sorted position t's process is in U(p)]: transpose U (lane q: the
+// receivers whose V holds q), fetch that column for position t's process, and transpose back
+// (two bit-matrix transposes and one shuffle; padding processes sort last and are in no U)
+PSG_DEV uint64_t sorted_members(uint64_t U, int32_t spid_r, int lane) {
+  const uint64_t Ut = wave_transpose64(U, lane);
+  return wave_transpose64((uint64_t)__shfl((unsigned long long)Ut, spid_r), lane);
+}
+
+// maxR of round 0 (Epsilon.scala:36): ceil(log(span / eps) / log(c)).toInt
+PSG_DEV int32_t eps_max_round(double span, double eps, double logc) {
+#pragma clang fp contract(off)
+  const double r1 = log_ocml(span / eps) / logc;
+  return d2i(ceil(r1));
+}
+
+// epsilon_kernel's sel8 table loop, by the whole block (the caller's barrier publishes it)
+PSG_DEV void build_sel8(uint8_t* sel8) {
+  for (uint32_t t = threadIdx.x; t < 256u * 8u; t += blockDim.x) {
+    uint32_t v = t >> 3, r = t & 7u;
+    for (; r > 0 && v != 0; --r) v &= v - 1u;  // drop r lowest set bits
+    sel8[t] = v ? (uint8_t)__builtin_ctz(v) : 0;
+  }
+}
+
+template <int W>
+PSG_DEV void selftest_grp(Grp<W>& g, int n, uint64_t* xb, int64_t* red) {
+  KArgs a = {};
+  a.n = n;
+  grp_setup(g, a, xb, red);
+}
+
+// out_f64 [3][count]: log_ocml(x), the device library's log(x), key_value(total_key(x));
+// out_i32 [3][count]: d2i(x), d2i(ceil(x)), fold32d(x)
+__global__ void __launch_bounds__(256) eps_f64_selftest_kernel(const double* x, int count, double* out_f64,
+                                                               int64_t* out_key, int32_t* out_i32) {
+  const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+  if (i >= count) return;
+  const size_t c = (size_t)count;
+  const double v = x[i];
+  const int64_t k = total_key(v);
+  out_f64[i] = log_ocml(v);
+  out_f64[c + i] = ::log(v);
+  out_f64[2 * c + i] = key_value(k);
+  out_key[i] = k;
+  out_i32[i] = d2i(v);
+  out_i32[c + i] = d2i(ceil(v));
+  out_i32[2 * c + i] = fold32d(v);
+}
+
+__global__ void __launch_bounds__(256) eps_maxr_selftest_kernel(const double* q, const double* c, int count, int32_t* out) {
+  const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+  if (i >= count) return;
+  out[i] = eps_max_round(q[i], 1.0, log_ocml(c[i]));
+}
+
+// network 0: the round kernel's sequence (wave_sort_values); 1: wave_sort_key_pid alone
+__global__ void __launch_bounds__(256) eps_sort_selftest_kernel(int network, const double* x, const int32_t* ns, int cases,
+                                                                double* out_x, int32_t* out_pid, int32_t* out_fell) {
+  const int cs = (int)(blockIdx.x * 4 + (threadIdx.x >> 6));
+  if (cs >= cases) return;  // (the whole wave)
+  Grp<1> g;
+  selftest_grp(g, rfl32(ns[cs]), nullptr, nullptr);
+  const size_t at = (size_t)cs * 64 + (size_t)g.lane;
+  const double v = x[at];
+  int32_t spid_r = g.lane;
+  bool fell = false;
+  double xs;
+  if (network == 0) {
+    xs = wave_sort_values(g, rfl32(ns[cs]), v, spid_r, fell);
+  } else {
+    int64_t skey = g.valid ? total_key(v) : INT64_MAX;
+    wave_sort_key_pid(skey, spid_r, g.lane);
+    xs = __shfl(v, spid_r);
+  }
+  out_x[at] = xs;
+  out_pid[at] = spid_r;
+  if (g.lane == 0) out_fell[cs] = fell ? 1 : 0;
+}
+
+// lane i of a case's wave supplies row i and receives column i
+__global__ void __launch_bounds__(256) eps_transpose_selftest_kernel(const uint64_t* rows, int cases, uint64_t* out) {
+  const int cs = (int)(blockIdx.x * 4 + (threadIdx.x >> 6));
+  if (cs >= cases) return;
+  const int lane = (int)(threadIdx.x & 63);
+  const size_t at = (size_t)cs * 64 + (size_t)lane;
+  out[at] = wave_transpose64(rows[at], lane);
+}
+
+// out [count][64]: RankSel(m).at(j) for j < popcount(m), then -1
+__global__ void __launch_bounds__(256) eps_select_selftest_kernel(const uint64_t* masks, int count, int32_t* out) {
+  __shared__ uint8_t sel8[256 * 8];
+  build_sel8(sel8);
+  __syncthreads();
+  const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+  if (i >= count) return;
+  const uint64_t m = masks[i];
+  const RankSel rs(m);
+  const uint32_t pop = (uint32_t)__popcll(m);
+  for (uint32_t j = 0; j < 64u; ++j) out[(size_t)i * 64 + j] = j < pop ? rs.at(j, sel8) : -1;
+}
+
+// lane p: U(p) and the process at sorted position p; out: Us(p)
+__global__ void __launch_bounds__(256) eps_members_selftest_kernel(const uint64_t* U, const int32_t* spid, int cases,
+                                                                   uint64_t* out) {
+  const int cs = (int)(blockIdx.x * 4 + (threadIdx.x >> 6));
+  if (cs >= cases) return;
+  const int lane = (int)(threadIdx.x & 63);
+  const size_t at = (size_t)cs * 64 + (size_t)lane;
+  out[at] = sorted_members(U[at], spid[at] & 63, lane);
+}
+
+// One block per case: v, in [cases][3][64W]; every reduction runs on the three data sets back to
+// back (W > 1: cross64's LDS phase flips between the calls). out [cases][9][W]: min64 x 3,
+// max64 x 3, sum64 x 3 as lane 0 of each wave holds them.
+template <int W>
+__global__ void __launch_bounds__(64 * W) eps_reduce_selftest_kernel(int n, const int64_t* v, const uint8_t* in, int64_t* out) {
+  __shared__ uint64_t xb[Grp<W>::kXb];
+  __shared__ int64_t red[2 * W];
+  Grp<W> g;
+  selftest_grp(g, n, xb, red);
+  const size_t base = (size_t)blockIdx.x * 3 * 64 * W + (size_t)g.pid;
+  int64_t vv[3], r[9];
+  bool ff[3];
+#pragma unroll
+  for (int s = 0; s < 3; ++s) {
+    vv[s] = v[base + (size_t)s * 64 * W];
+    ff[s] = in[base + (size_t)s * 64 * W] != 0;
+  }
+#pragma unroll
+  for (int s = 0; s < 3; ++s) r[s] = g.min64(vv[s], ff[s]);
+#pragma unroll
+  for (int s = 0; s < 3; ++s) r[3 + s] = g.max64(vv[s], ff[s]);
+#pragma unroll
+  for (int s = 0; s < 3; ++s) r[6 + s] = (int64_t)g.sum64((uint64_t)vv[s]);
+  if (g.lane == 0) {
+#pragma unroll
+    for (int j = 0; j < 9; ++j) out[((size_t)blockIdx.x * 9 + j) * W + g.wv] = r[j];
+  }
+}
+
+hipError_t launch_eps_selftest_f64(const double* x, int count, double* out_f64, int64_t* out_key, int32_t* out_i32,
+                                   hipStream_t s) {
+  hipLaunchKernelGGL(eps_f64_selftest_kernel, dim3((count + 255) / 256), dim3(256), 0, s, x, count, out_f64, out_key, out_i32);
+  return hipGetLastError();
+}
+hipError_t launch_eps_selftest_maxr(const double* q, const double* c, int count, int32_t* out, hipStream_t s) {
+  hipLaunchKernelGGL(eps_maxr_selftest_kernel, dim3((count + 255) / 256), dim3(256), 0, s, q, c, count, out);
+  return hipGetLastError();
+}
+hipError_t launch_eps_selftest_sort(int network, const double* x, const int32_t* ns, int cases, double* out_x,
+                                    int32_t* out_pid, int32_t* out_fell, hipStream_t s) {
+  hipLaunchKernelGGL(eps_sort_selftest_kernel, dim3((cases + 3) / 4), dim3(256), 0, s, network, x, ns, cases, out_x, out_pid,
+                     out_fell);
+  return hipGetLastError();
+}
+hipError_t launch_eps_selftest_transpose(const uint64_t* rows, int cases, uint64_t* out, hipStream_t s) {
+  hipLaunchKernelGGL(eps_transpose_selftest_kernel, dim3((cases + 3) / 4), dim3(256), 0, s, rows, cases, out);
+  return hipGetLastError();
+}
+hipError_t launch_eps_selftest_select(const uint64_t* masks, int count, int32_t* out, hipStream_t s) {
+  hipLaunchKernelGGL(eps_select_selftest_kernel, dim3((count + 255) / 256), dim3(256), 0, s, masks, count, out);
+  return hipGetLastError();
+}
+hipError_t launch_eps_selftest_members(const uint64_t* U, const int32_t* spid, int cases, uint64_t* out, hipStream_t s) {
+  hipLaunchKernelGGL(eps_members_selftest_kernel, dim3((cases + 3) / 4), dim3(256), 0, s, U, spid, cases, out);
+  return hipGetLastError();
+}
+hipError_t launch_eps_selftest_reduce(int W, int n, const int64_t* v, const uint8_t* in, int cases, int64_t* out, hipStream_t s) {
+  return with_w(W, hipErrorInvalidValue, [&](auto w) {
+    hipLaunchKernelGGL(eps_reduce_selftest_kernel<w()>, dim3(cases), dim3(64 * w()), 0, s, n, v, in, out);
+    return hipGetLastError();
+  });
 }
 
 }  // namespace psg

@@ -55,6 +55,16 @@ const void* otr_plain_kernel_ptr(int W);
 const void* otr2_plain_kernel_ptr(int W);
 
 hipError_t launch_champ_selftest(const uint64_t* sets, int count, int tiebreak, int32_t* out, hipStream_t s);
+// self-tests of the EpsilonConsensus kernel's building blocks (psg_epsilon.hip, psg_selftest_eps_*)
+hipError_t launch_eps_selftest_f64(const double* x, int count, double* out_f64, int64_t* out_key, int32_t* out_i32,
+                                   hipStream_t s);
+hipError_t launch_eps_selftest_maxr(const double* q, const double* c, int count, int32_t* out, hipStream_t s);
+hipError_t launch_eps_selftest_sort(int network, const double* x, const int32_t* ns, int cases, double* out_x,
+                                    int32_t* out_pid, int32_t* out_fell, hipStream_t s);
+hipError_t launch_eps_selftest_transpose(const uint64_t* rows, int cases, uint64_t* out, hipStream_t s);
+hipError_t launch_eps_selftest_select(const uint64_t* masks, int count, int32_t* out, hipStream_t s);
+hipError_t launch_eps_selftest_members(const uint64_t* U, const int32_t* spid, int cases, uint64_t* out, hipStream_t s);
+hipError_t launch_eps_selftest_reduce(int W, int n, const int64_t* v, const uint8_t* in, int cases, int64_t* out, hipStream_t s);
 hipError_t launch_schedule(const KArgs& a, int W, int grid, uint64_t* ho_out, int32_t* crash_out, hipStream_t s);
 hipError_t launch_population(const PopArgs& a, hipStream_t s);
 // population models: the forced live rounds over a.ho (after launch_population), a crash-family

@@ -32,6 +32,8 @@ EXPORTED_SYMBOLS = [
     "psg_shrink_read",
     "psg_spec_compile_native", "psg_spec_native_source", "psg_selftest_bitset", "psg_spec_rewrite_text",
     "psg_spec_set_options", "psg_pack_width",
+    "psg_selftest_eps_f64", "psg_selftest_eps_maxr", "psg_selftest_eps_sort", "psg_selftest_eps_transpose",
+    "psg_selftest_eps_select", "psg_selftest_eps_members", "psg_selftest_eps_reduce",
 ]
 
 
@@ -109,6 +111,15 @@ def load():
         L.psg_shrink_load.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64]
         L.psg_shrink_adopt.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.c_uint64]
         L.psg_shrink_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.psg_selftest_eps_f64.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.psg_selftest_eps_maxr.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        L.psg_selftest_eps_sort.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                            C.c_void_p, C.c_void_p]
+        L.psg_selftest_eps_transpose.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+        L.psg_selftest_eps_select.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+        L.psg_selftest_eps_members.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        L.psg_selftest_eps_reduce.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                              C.c_void_p]
     except AttributeError:
         pass
     L.psg_spec_release.argtypes = [C.POINTER(abi.SpecProgram)]
@@ -471,6 +482,103 @@ def selftest_bitset(ops, W=1, device=0):
     if rc != 0:
         raise PsgError(rc, "psg_selftest_bitset failed")
     return list(out)[:n_out]
+
+
+def _st_in(a, dtype, shape=None):
+    """A contiguous array of a self-test's input (doubles keep their bits when given as uint64)."""
+    import numpy as np
+    a = np.asarray(a)
+    if dtype == np.float64 and a.dtype == np.uint64:
+        a = a.view(np.float64)
+    a = np.ascontiguousarray(a, dtype=dtype)
+    if shape is not None and a.shape != shape:
+        raise ValueError(f"expected shape {shape}, got {a.shape}")
+    return a
+
+
+def _st_call(name, *args):
+    rc = getattr(load(), name)(*[a.ctypes.data_as(C.c_void_p) if hasattr(a, "ctypes") else a for a in args])
+    if rc != 0:
+        raise PsgError(rc, f"{name} failed")
+
+
+def selftest_eps_f64(x, device=0):
+    """psg_selftest_eps_f64 on doubles x (float64, or uint64 bit patterns). Returns a dict of arrays:
+    log_ocml, log (the device library's), key (int64), key_value, d2i, d2i_ceil, fold32."""
+    import numpy as np
+    x = _st_in(x, np.float64)
+    k = x.size
+    f, key, i = np.zeros((3, k), np.float64), np.zeros(k, np.int64), np.zeros((3, k), np.int32)
+    _st_call("psg_selftest_eps_f64", device, x, k, f, key, i)
+    return dict(log_ocml=f[0], log=f[1], key=key, key_value=f[2], d2i=i[0], d2i_ceil=i[1], fold32=i[2])
+
+
+def selftest_eps_maxr(q, c, device=0):
+    """psg_selftest_eps_maxr: int32 (int) ceil(log(q) / log(c)) per pair, as round 0 forms maxR."""
+    import numpy as np
+    q = _st_in(q, np.float64)
+    c = _st_in(c, np.float64, q.shape)
+    out = np.zeros(q.size, np.int32)
+    _st_call("psg_selftest_eps_maxr", device, q, c, q.size, out)
+    return out
+
+
+def selftest_eps_sort(x, n, network=0, device=0):
+    """psg_selftest_eps_sort: x [cases][64] doubles (or uint64 bits), n [cases]. Returns (values as
+    uint64 bits [cases][64], pid int32 [cases][64], fallback int32 [cases]); network 1 runs the
+    (key, pid) network alone."""
+    import numpy as np
+    n = _st_in(n, np.int32)
+    x = _st_in(x, np.float64, (n.size, 64))
+    ox, pid, fell = np.zeros((n.size, 64), np.float64), np.zeros((n.size, 64), np.int32), np.zeros(n.size, np.int32)
+    _st_call("psg_selftest_eps_sort", device, network, x, n, n.size, ox, pid, fell)
+    return ox.view(np.uint64), pid, fell
+
+
+def selftest_eps_transpose(rows, device=0):
+    """psg_selftest_eps_transpose: uint64 [cases][64] -> the transposed bit matrices."""
+    import numpy as np
+    rows = _st_in(rows, np.uint64)
+    if rows.ndim != 2 or rows.shape[1] != 64:
+        raise ValueError("rows must be [cases][64]")
+    out = np.zeros_like(rows)
+    _st_call("psg_selftest_eps_transpose", device, rows, rows.shape[0], out)
+    return out
+
+
+def selftest_eps_select(masks, device=0):
+    """psg_selftest_eps_select: non-zero uint64 masks -> int32 [count][64], the position of the j-th
+    set bit for j < popcount, then -1."""
+    import numpy as np
+    masks = _st_in(masks, np.uint64)
+    out = np.zeros((masks.size, 64), np.int32)
+    _st_call("psg_selftest_eps_select", device, masks, masks.size, out)
+    return out
+
+
+def selftest_eps_members(U, spid, device=0):
+    """psg_selftest_eps_members: U uint64 [cases][64], spid int32 [cases][64] -> Us uint64 [cases][64]."""
+    import numpy as np
+    U = _st_in(U, np.uint64)
+    if U.ndim != 2 or U.shape[1] != 64:
+        raise ValueError("U must be [cases][64]")
+    spid = _st_in(spid, np.int32, U.shape)
+    out = np.zeros_like(U)
+    _st_call("psg_selftest_eps_members", device, U, spid, U.shape[0], out)
+    return out
+
+
+def selftest_eps_reduce(W, n, v, flags, device=0):
+    """psg_selftest_eps_reduce: v int64 and flags uint8 [cases][3][64W] -> int64 [cases][9][W]:
+    min64 of the three sets, max64, sum64, per wave."""
+    import numpy as np
+    v = _st_in(v, np.int64)
+    if v.ndim != 3 or v.shape[1:] != (3, 64 * W):
+        raise ValueError("v must be [cases][3][64W]")
+    flags = _st_in(flags, np.uint8, v.shape)
+    out = np.zeros((v.shape[0], 9, W), np.int64)
+    _st_call("psg_selftest_eps_reduce", device, W, n, v, flags, v.shape[0], out)
+    return out
 
 
 def spec_from_text(text, alg=0):
