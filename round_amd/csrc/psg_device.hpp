@@ -86,9 +86,12 @@ inline bool plain_schedule(const KArgs& a) { return PSG_PLAIN_SCHEDULE && a.cras
 
 // Global instance id of batch element i: the explicit id list, else consecutive ids.
 PSG_DEV uint64_t instance_id(const KArgs& a, uint64_t i) { return a.ids ? a.ids[i] : a.inst_begin + i; }
+// (has_ids: a.ids != nullptr as the caller holds it, e.g. a bit of its launch word)
+PSG_DEV uint64_t instance_id(const KArgs& a, uint64_t i, bool has_ids) { return has_ids ? a.ids[i] : a.inst_begin + i; }
 // Initial value of process pid of batch element i (global id inst): staged rows
 // are indexed by batch position, or by global id in the fetch (ids) path.
 PSG_DEV uint64_t init_row(const KArgs& a, uint64_t i, uint64_t inst) { return a.ids ? inst - a.init_base : i; }
+PSG_DEV uint64_t init_row(const KArgs& a, uint64_t i, uint64_t inst, bool has_ids) { return has_ids ? inst - a.init_base : i; }
 // Host-supplied initial value of process pid (a.init non-null). The pid term of the address is
 // formed here per instance (opaque copy), not hoisted out of the instance loop and kept live.
 PSG_DEV int32_t init_x(const KArgs& a, uint64_t i, uint64_t inst, int pid) {
@@ -1395,13 +1398,16 @@ struct Inst {
   // begin() without the first block of good rounds, for the kernels that read them from a
   // GoodFront (below)
   PSG_DEV void begin_front(Grp<W>& g, const KArgs& a, uint64_t i, int32_t* crl) {
-    id = instance_id(a, i);
+    begin_front(g, a, i, crl, a.ids != nullptr);
+  }
+  PSG_DEV void begin_front(Grp<W>& g, const KArgs& a, uint64_t i, int32_t* crl, bool has_ids) {
+    id = instance_id(a, i, has_ids);
     sc.setup(a, id, g.pid, g.valid);
     if (sc.crash_on) cs.prep(g, crl, sc.crash_round);
   }
   // begin_front() of a plain schedule (Sched::setup_plain): no crash draw, no crash sets
-  PSG_DEV void begin_plain(const KArgs& a, uint64_t i) {
-    id = instance_id(a, i);
+  PSG_DEV void begin_plain(const KArgs& a, uint64_t i, bool has_ids) {
+    id = instance_id(a, i, has_ids);
     sc.setup_plain(a, id);
   }
   // Initial value of this lane's process: host-supplied, else seeded (0 for lanes past n)
@@ -1468,7 +1474,7 @@ struct GoodFront {
   // At the start of batch row i (uniform; sc set up for it): a new front block when the row is
   // outside the one held. Rows come from the queue in increasing runs of a chunk. The lane's
   // row and round are formed here per block (opaque copy), not hoisted out of the instance loop.
-  PSG_DEV void start(const Sched<1, false>& sc, const KArgs& a, uint64_t i, int lane) {
+  PSG_DEV void start(const Sched<1, false>& sc, const KArgs& a, uint64_t i, int lane, bool has_ids) {
     base = kRounds - kLate;
     if (i - g0 < (uint64_t)kRows) return;
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -1476,9 +1482,9 @@ struct GoodFront {
 #endif
     g0 = i;
     uint64_t row = i + (uint64_t)(lane & (kRows - 1));
-    if (a.ids && row >= a.count) row = a.count - 1;  // the id list ends at a.count (i < a.count)
+    if (has_ids && row >= a.count) row = a.count - 1;  // the id list ends at a.count (i < a.count)
     uint64_t s;
-    const bool good = pass(sc, instance_id(a, row), ((uint32_t)lane >> 3) & (uint32_t)(kRounds - 1), lane, a.R, s);
+    const bool good = pass(sc, instance_id(a, row, has_ids), ((uint32_t)lane >> 3) & (uint32_t)(kRounds - 1), lane, a.R, s);
     set = fold(s, lane);
     mask = (uint32_t)__builtin_amdgcn_ballot_w64(good);
   }
@@ -1679,9 +1685,52 @@ struct WaveTally {
   }
 };
 
+// Launch-constant predicates of a kernel as bits of one 32-bit scalar word, formed once per kernel
+// (launch_bits) and tested where used. As separate uniform bools hoisted out of the instance loop
+// each is a 64-bit lane mask: two scalar registers, spilled and reloaded per instance.
+struct LaunchBits {
+  static constexpr uint32_t kDecision = 1u << 0;  // a.out_decision
+  static constexpr uint32_t kDround = 1u << 1;    // a.out_dround
+  static constexpr uint32_t kInst = 1u << 2;      // a.out_inst
+  static constexpr uint32_t kRec = 1u << 3;       // a.out_rec
+  static constexpr uint32_t kOutputs = kDecision | kDround | kInst | kRec;
+  static constexpr uint32_t kInit = 1u << 4;      // a.init
+  static constexpr uint32_t kIds = 1u << 5;       // a.ids
+  static constexpr uint32_t kGood = 1u << 6;      // a.good_p32 != 0
+  // the library's ordinary output shape: decision, decide round and summary, no process record
+  static constexpr uint32_t kOrdinary = 1u << 7;
+  static constexpr uint32_t kWideV = 1u << 8;     // a.V > 64: X0Set::build_window goes to the hash table
+};
+PSG_DEV uint32_t launch_bits(const KArgs& a) {
+  uint32_t b = (a.out_decision ? LaunchBits::kDecision : 0u) | (a.out_dround ? LaunchBits::kDround : 0u) |
+               (a.out_inst ? LaunchBits::kInst : 0u) | (a.out_rec ? LaunchBits::kRec : 0u) |
+               (a.init ? LaunchBits::kInit : 0u) | (a.ids ? LaunchBits::kIds : 0u) |
+               (a.good_p32 != 0 ? LaunchBits::kGood : 0u) | (a.V > 64 ? LaunchBits::kWideV : 0u);
+  if ((b & LaunchBits::kOutputs) == (LaunchBits::kDecision | LaunchBits::kDround | LaunchBits::kInst))
+    b |= LaunchBits::kOrdinary;
+  return opaque_uniform(b);
+}
+// The word carried through the instance loop: called once per instance on the kernel's word, it
+// makes the word a loop-carried value (an empty volatile asm that "rewrites" it in place, no
+// instruction), so that a bit test of it is formed beside its branch — one scalar bit compare —
+// and is not hoisted out of the loop, where every hoisted test is a 64-bit lane mask again.
+PSG_DEV uint32_t launch_bits_carry(uint32_t lb) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("" : "+s"(lb));
+#endif
+  return lb;
+}
+PSG_DEV uint32_t launch_bit01(uint32_t lb, uint32_t bit) { return lb & bit; }
+
 // finish_instance for W == 1 kernels that keep a StepTally and a WaveTally and know the
 // instance's live rounds: the same outputs, byte for byte.
-// - The digest sum is a DPP scan (Grp::wave_scan_sum64): the total stays in lane 63.
+// - The digest sum is a DPP scan (Grp::wave_scan_sum64): the total stays in lane 63. (A reduction
+//   into lane 63 over three limb sums, one v_add_u32_dpp per step and no wait states, is 13
+//   instructions shorter in the listing and measured 1.3 % slower on the headline: DESIGN §5.)
+// - lb: the kernel's launch_bits. The ordinary output shape (LaunchBits::kOrdinary) takes an arm
+//   of its own: the decision and decide-round stores straight-line under the valid-lane
+//   predicate and the summary store under its lane test, no uniform branch around any of them.
+//   Every other combination of present and absent arrays takes the per-array tests.
 // - The 24-byte psg_instance_summary leaves as one 8-byte store from three lanes under one
 //   predicate: lane 63 the digest (bytes 0-7), lane 0 bytes 8-15, lane 8 bytes 16-23. Lane s of
 //   ck.ffv holds first_fail[s] (s < 12), i.e. bytes 8-19 in lane order: lane 4q gathers its
@@ -1692,7 +1741,8 @@ struct WaveTally {
 //   to the one bin); the other counters go through the WaveTally.
 PSG_DEV void finish_instance_w1(Grp<1>& g, const KArgs& a, uint64_t i, const Checks& ck, int nchecks, int32_t dec_val,
                                 int32_t dec_round, int32_t halt_round, int32_t main_x, BlockCounters* bc,
-                                StepTally* tally, WaveTally* wt, int32_t live_rounds, PhaseTimers* pt = nullptr) {
+                                StepTally* tally, WaveTally* wt, int32_t live_rounds, uint32_t lb,
+                                PhaseTimers* pt = nullptr) {
   static_assert(PSG_MAX_CHECKS == 12 && sizeof(psg_instance_summary) == 24, "summary record layout");
   const int n = a.n;
   const bool decided = dec_round >= 0;
@@ -1701,19 +1751,6 @@ PSG_DEV void finish_instance_w1(Grp<1>& g, const KArgs& a, uint64_t i, const Che
   if (pt) pt->mark(7);
   const int nd = mpopc(g.ballot(decided));
   tally->add(g.valid ? (halt_round >= 0 ? halt_round + 1 : a.R) : 0);
-  if (g.valid) {
-    const uint64_t off = i * (uint64_t)n + (uint64_t)g.pid;
-    if (a.out_decision) a.out_decision[off] = dec_val;
-    if (a.out_dround) a.out_dround[off] = decided ? (uint8_t)dec_round : (uint8_t)0xFF;
-    if (a.out_rec) {
-      psg_process_record r;
-      r.decision = dec_val;
-      r.decision_round = dec_round;
-      r.halt_round = halt_round;
-      r.final_x = main_x;
-      a.out_rec[off] = r;
-    }
-  }
   uint32_t lane = (uint32_t)g.lane;
 #if defined(__HIP_DEVICE_COMPILE__)
   // opaque copy: the lane tests and the store offset are formed here per instance, not hoisted
@@ -1731,15 +1768,45 @@ PSG_DEV void finish_instance_w1(Grp<1>& g, const KArgs& a, uint64_t i, const Che
   const uint32_t lo = last ? (uint32_t)scan : w0, hi = last ? (uint32_t)(scan >> 32) : w1;
   // lanes 0, 8, 63 (byte offsets 8, 16, 0), as one bit test: a disjunction of lane compares
   // compiles to nested exec regions
-  if ((0x8000000000000101ull >> lane) & 1ull) {
-    if (a.out_inst) {
-      uint8_t* o = reinterpret_cast<uint8_t*>(a.out_inst + i);
-      *reinterpret_cast<uint64_t*>(o + ((lane + 8u) & 24u)) = (uint64_t)lo | ((uint64_t)hi << 32);
+  const bool sumlane = ((0x8000000000000101ull >> lane) & 1ull) != 0ull;
+  auto put_summary = [&] {
+    uint8_t* o = reinterpret_cast<uint8_t*>(a.out_inst + i);
+    *reinterpret_cast<uint64_t*>(o + ((lane + 8u) & 24u)) = (uint64_t)lo | ((uint64_t)hi << 32);
+  };
+  // (the valid-lane predicate of the stores from the opaque lane: one compare here, where
+  // g.valid's lane mask is a pair of spilled scalars at this point)
+  const bool valid = lane < (uint32_t)n;
+  if (launch_bit01(lb, LaunchBits::kOrdinary)) {
+    if (valid) {
+      const uint64_t off = i * (uint64_t)(uint32_t)n + (uint64_t)lane;
+      a.out_decision[off] = dec_val;
+      a.out_dround[off] = decided ? (uint8_t)dec_round : (uint8_t)0xFF;
     }
-    // (the bin index in a VGPR: with a uniform address the compiler sums the three addends in a
-    // scalar loop over the active lanes first)
-    atomicAdd(&bc->hist[vgpr_u32(term == PSG_NEVER ? (uint32_t)a.R + 1u : term)], last ? 1u : 0u);
+    if (sumlane) put_summary();
+  } else {
+    if (valid) {
+      const uint64_t off = i * (uint64_t)(uint32_t)n + (uint64_t)lane;
+      if (launch_bit01(lb, LaunchBits::kDecision)) a.out_decision[off] = dec_val;
+      if (launch_bit01(lb, LaunchBits::kDround)) a.out_dround[off] = decided ? (uint8_t)dec_round : (uint8_t)0xFF;
+      if (launch_bit01(lb, LaunchBits::kRec)) {
+        psg_process_record r;
+        r.decision = dec_val;
+        r.decision_round = dec_round;
+        r.halt_round = halt_round;
+        r.final_x = main_x;
+        a.out_rec[off] = r;
+      }
+    }
+    if (sumlane && launch_bit01(lb, LaunchBits::kInst)) put_summary();
   }
+  // The bin is term, or R + 1 for PSG_NEVER, formed as 1 + min(term - 1, R) (term <= R unless
+  // PSG_NEVER, and PSG_NEVER - 1 > R): R is live in the kernel where R + 1 would be one more
+  // launch constant to reload, and the 1 folds into the LDS offset.
+  // (the bin index in a VGPR: with a uniform address the compiler sums the three addends in a
+  // scalar loop over the active lanes first)
+  static_assert(PSG_NEVER - 1 > PSG_MAX_ROUNDS, "PSG_NEVER lands in bin R + 1");
+  const int32_t bin_m1 = (int32_t)term - 1 < a.R ? (int32_t)term - 1 : a.R;
+  if (sumlane) atomicAdd(&bc->hist[1 + (int32_t)vgpr_u32((uint32_t)bin_m1)], last ? 1u : 0u);
   wt->add((int)lane, scan, ck, nd, live_rounds);
 }
 
@@ -1908,9 +1975,10 @@ struct X0Set {
   // and one ballot of the marks is the word (a wave's LDS operations execute in order). Lanes
   // past n (x0 = 0) are masked out of the test and mark slot 64 + lane, which nobody reads.
   // A miss (host-supplied values outside the window) is build() unchanged.
-  PSG_DEV void build_window(Grp<W>& g, int32_t* lds, int32_t x0, int32_t V) {
+  // wide: the launch's V > 64 (LaunchBits::kWideV)
+  PSG_DEV void build_window(Grp<W>& g, int32_t* lds, int32_t x0, bool wide) {
     static_assert(W == 1, "the window form is W == 1 only");
-    if (V > 64 || g.any((uint32_t)(x0 - 1) >= 64u)) {
+    if (wide || g.any((uint32_t)(x0 - 1) >= 64u)) {
       build(g, lds, x0);
       return;
     }

@@ -349,6 +349,17 @@ PSG_DEV void otr_body(const KArgs& a) {
   const int32_t ckthr = W == 1 ? otr_check_thresholds<V2>(n, g.lane) : 0;  // (W > 1: unused)
   // PLAIN: the lane's self bit as a word of the HO set, 0 when the schedule has none
   const uint64_t selfw = PLAIN && a.self_bit ? 1ull << (g.pid & 63) : 0ull;
+  // W == 1: the launch-constant predicates of the setup and the finish as bits of one scalar
+  // word (LaunchBits, psg_device.hpp)
+  uint32_t lb = W == 1 ? launch_bits(a) : 0u;
+  auto has_ids = [&]() -> bool {
+    if constexpr (W == 1) return launch_bit01(lb, LaunchBits::kIds) != 0u;
+    else return a.ids != nullptr;
+  };
+  auto has_init = [&]() -> bool {
+    if constexpr (W == 1) return launch_bit01(lb, LaunchBits::kInit) != 0u;
+    else return a.init != nullptr;
+  };
 
   // profiling builds only: t1 active round, t2 frozen round; the setup is t4 queue take, t5 begin +
   // initial value, t6 X0 set, t0 check point 0; the finish t7 digest and its sum, t3 the rest.
@@ -364,31 +375,33 @@ PSG_DEV void otr_body(const KArgs& a) {
   // issued when an instance starts and consumed when the next one does, so its latency
   // overlaps the current instance's rounds instead of stalling its setup.
   auto load_x0 = [&](uint64_t ii) -> int32_t {
-    if (ii == Q.kDone || !a.init || !g.valid) return 0;
-    return a.init[init_row(a, ii, instance_id(a, ii)) * (uint64_t)n + g.pid];
+    if (ii == Q.kDone || !has_init() || !g.valid) return 0;
+    return a.init[init_row(a, ii, instance_id(a, ii, has_ids()), has_ids()) * (uint64_t)n + g.pid];
   };
   uint64_t inext = Q.take(a);
   int32_t x0next = load_x0(inext);
   while (inext != Q.kDone) {
     const uint64_t i = inext;
     const int32_t x0host = x0next;
+    if constexpr (W == 1) lb = launch_bits_carry(lb);
     inext = Q.take(a);
     x0next = load_x0(inext);
     pt.mark(4);
     Inst<W, XHO> in;
     if constexpr (kFront) {
-      if constexpr (PLAIN) in.begin_plain(a, i);
-      else in.begin_front(g, a, i, crl);
-      if (a.good_p32 != 0) gf.start(in.sc, a, i, g.lane);
+      if constexpr (PLAIN) in.begin_plain(a, i, has_ids());
+      else in.begin_front(g, a, i, crl, has_ids());
+      if (launch_bit01(lb, LaunchBits::kGood)) gf.start(in.sc, a, i, g.lane, has_ids());
     } else {
       in.begin(g, a, i, crl);
     }
     Sched<W, XHO>& sc = in.sc;
     int32_t x0 = 0;
-    if (g.valid) x0 = a.init ? x0host : sc.init_value(g.pid, PSG_ALG_OTR);
+    if (g.valid) x0 = has_init() ? x0host : sc.init_value(g.pid, PSG_ALG_OTR);
     pt.mark(5);
     X0Set<W> X0;
-    if constexpr (W == 1) X0.build_window(g, x0tab[grp], x0, a.V);
+    if constexpr (W == 1)
+      X0.build_window(g, x0tab[grp], x0, launch_bit01(lb, LaunchBits::kWideV) != 0u);
     else X0.build(g, x0tab[grp], x0);
     pt.mark(6);
     // OtrProcess state after init(io) (Otr.scala:15-26); flags are 0/1 lane words
@@ -579,7 +592,7 @@ PSG_DEV void otr_body(const KArgs& a) {
     pt.add(6, 1u);  // event build: instances
     if constexpr (W == 1)
       finish_instance_w1(g, a, i, hook_checks<SH>(sh, ck), hook_slots<SH>(kOtrChecks), dec_val, dec_round, halt_round, x,
-                         &bc, &tally, &wtally, live_rounds, &pt);
+                         &bc, &tally, &wtally, live_rounds, lb, &pt);
     else
       finish_instance<W>(g, a, i, hook_checks<SH>(sh, ck), hook_slots<SH>(kOtrChecks), dec_val, dec_round, halt_round, x,
                          &bc, &tally, live_rounds, &pt);
