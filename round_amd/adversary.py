@@ -9,11 +9,12 @@ environment assumptions (psync/verification/Verifier.scala:145-168: the
 rounds of a progress step). Here the same assumptions constrain explicit HO
 schedules (round_amd/schedules.py) and the GPU executes and checks
 populations of them per launch (psg_load_schedule + psg_run_batch), so a
-search is a loop of: generate / mutate schedules on the host, run them all on
-the device, keep the ones that get closest to a violation. (Device-resident
-populations, psg_population_*, generate and mutate on the GPU instead: the
-general-omission safety search always, the crash family and the liveness search
-with device_models=True.)
+search is one loop (Adversary.search) of: run a population on the device, keep
+the schedules that get closest to a violation, mutate them. Where the
+population lives is behind one interface: _HostPopulation generates and mutates
+with numpy and uploads every generation, _DevicePopulation keeps it in HBM
+(psg_population_*: the general-omission safety search always, the crash family
+and the liveness search with device_models=True).
 
   * safety search: schedules satisfy the safety predicate on their HO sets;
     a violation of a target check slot is genuine only while the predicate
@@ -27,13 +28,15 @@ with device_models=True.)
     BenOr, EpsilonConsensus, TwoPhaseCommit, LatticeAgreement) or crash-stop with at most f crashes (FloodMin,
     KSetAgreement, KSetEarlyStopping — their runners' fault model).
 Every counterexample is shrunk (batched delta debugging: all candidate
-simplifications of one step run as one GPU batch; with device_shrink=True the
-candidates are written on the device too, psg_shrink_*, and only the shrunk
-schedule comes back) and can be written to a .psgr file (round_amd/records.py)
+simplifications of one step run as one GPU batch). One driver holds the plan
+and the selection rule (Adversary._shrink_plan); a step of it either builds the
+candidates on the host (schedules.shrink_candidates) or, with
+device_shrink=True, on the device (psg_shrink_*, only the shrunk schedule comes
+back). Counterexamples can be written to a .psgr file (round_amd/records.py)
 that `records.replay` re-executes.
 """
 import time
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 from typing import Callable, List, Optional, Sequence
 
 import numpy as np
@@ -41,6 +44,18 @@ import numpy as np
 from . import abi, psync, records, schedules as S
 
 NEVER = abi.PSG_NEVER
+
+# The generators' constants: the host generators use them as they are, the device ones
+# (psg_population_params / psg_population_model) in /256 fixed point.
+LOSS_SPREAD = (0.7, 0.85, 1.0, 1.15)       # a fresh population's loss rates around `keep`, one per quarter
+CRASH_DELIVERY = (0.05, 0.15, 0.5, 0.85)   # crash family: densities of the crash-round deliveries
+FLIP_STRENGTH = 0.01                       # links flipped in a mutant, as a share of n * R (at least one)
+INIT_REDRAW = 0.02                         # share of a mutant's initial values drawn again
+CRASH_MUTATE = 0.3                         # schedules.mutate_crash: move and add w.p. this each, drop w.p. half
+
+
+def _p256(p: float) -> int:
+    return int(round(p * 256))
 
 
 # ------------------------------------------------------------------ evaluation
@@ -153,6 +168,15 @@ class Counterexample:
     check_point: int                 # first check point of the violation
     omitted_links: int = 0           # links missing from the HO sets (self links excluded)
 
+    def same(self, other: "Counterexample") -> bool:
+        """The same counterexample bit for bit, every field."""
+        def eq(a, b):
+            return (a is None) == (b is None) and (a is None or np.array_equal(a, b))
+        return bool(self.inst_id == other.inst_id and eq(self.init, other.init) and eq(self.ho, other.ho)
+                    and eq(self.crash, other.crash) and self.violated == other.violated
+                    and self.check_point == other.check_point and self.omitted_links == other.omitted_links
+                    and np.asarray(self.summary).tobytes() == np.asarray(other.summary).tobytes())
+
 
 @dataclass
 class SearchResult:
@@ -166,6 +190,109 @@ class SearchResult:
     @property
     def schedules_per_second(self):
         return self.schedules_evaluated / self.seconds if self.seconds > 0 else 0.0
+
+
+# ------------------------------------------------------------------ populations
+# What Adversary.search needs of a population: fresh() makes generation 0; evaluate() runs it and
+# returns (Eval, valid [P], seconds on the GPU), valid[i] = instance i satisfies the model's
+# constraints, and sets `base`, the instance id of row 0; read(rows) returns (init, ho, crash) of
+# these rows; advance(elite, parents, n_fresh, generation) replaces it by the elite rows, one
+# mutant per parent row and n_fresh fresh schedules, in this order, and returns its GPU seconds.
+
+class _HostPopulation:
+    """Genome and initial values as numpy arrays, drawn from the adversary's generator; every
+    generation is uploaded and runs under an instance id block of its own."""
+
+    def __init__(self, adv: "Adversary"):
+        self.adv = adv
+
+    def fresh(self):
+        a = self.adv
+        self.genome = a._fresh(a.population)
+        self.init = default_init(a.alg, a.rng, a.population, a.n, a.values)
+
+    def evaluate(self):
+        a = self.adv
+        self.ho, self.crash, valid = a._realize(self.genome)
+        self.base = a.next_id
+        a.next_id += a.population
+        t = time.perf_counter()
+        ev = a.evaluator(self.base, self.ho, self.crash, self.init)
+        return ev, valid, time.perf_counter() - t
+
+    def read(self, rows):
+        return self.init[rows], self.ho[rows], None if self.crash is None else self.crash[rows]
+
+    def advance(self, elite, parents, n_fresh, generation):
+        a = self.adv
+        children = a._mutate(a._take(self.genome, parents), max(1, int(a.n * a.R * FLIP_STRENGTH)))
+        genome = a._cat(a._take(self.genome, elite), children)
+        self.genome = a._cat(genome, a._fresh(n_fresh)) if n_fresh else genome
+        cinit = self.init[parents].copy()
+        flip = a.rng.random(cinit.shape) < INIT_REDRAW
+        cinit[flip] = default_init(a.alg, a.rng, len(parents), a.n, a.values)[flip]
+        self.init = np.concatenate([self.init[elite], cinit, default_init(a.alg, a.rng, n_fresh, a.n, a.values)])
+        return 0.0
+
+
+class _DevicePopulation:
+    """The population resident in HBM (psg_population_*), generated and mutated there from one
+    seed under one instance id block: per generation the per-instance summaries and decisions
+    come to the host and the chosen parents go back (no HO set crosses PCIe but a counterexample's)."""
+
+    def __init__(self, adv: "Adversary"):
+        self.adv, self.ctx, self.pm = adv, adv.evaluator.gr._ctx, adv._pop_model()
+
+    def _params(self, generation):
+        a = self.adv
+        p = abi.PopulationParams()
+        p.seed, p.generation = self.seed, generation
+        # (crash family: one crash-round delivery toggled per mutant, as schedules.mutate_crash)
+        p.flips = 1 if a.model.family == "crash" else max(1, int(a.n * a.R * FLIP_STRENGTH))
+        p.min_size = a.model.min_size or 0
+        p.self_bit = 1 if a.self_bit else 0
+        for j, kp in enumerate(a._keep_levels()):
+            p.keep_p256[j] = _p256(kp)
+        p.value_range = a.values
+        p.redraw_p256 = _p256(INIT_REDRAW)
+        return p
+
+    def fresh(self):
+        a = self.adv
+        self.base = a.next_id
+        a.next_id += a.population
+        self.seed = int(a.rng.integers(0, 1 << 63))
+        if self.pm is None:
+            self.ctx.population_fresh(self.base, a.population, self._params(0))
+        else:
+            self.ctx.population_fresh_model(self.base, a.population, self._params(0), self.pm)
+
+    def evaluate(self):
+        a, pm = self.adv, self.pm
+        t = time.perf_counter()
+        _, pi = self.ctx.run_batch_np(self.base, a.population)
+        dec, dr = self.ctx.copy_decisions_np()
+        valid = np.ones(a.population, bool)
+        if a.mode == "liveness":  # only instances with enough live rounds count
+            valid = self.ctx.population_live(pm.live_kind, pm.phase, pm.coord).sum(1) >= a.live_rounds
+        return Eval(pi, dec, dr), valid, time.perf_counter() - t
+
+    def read(self, rows):
+        hos, inits = self.ctx.population_read(rows)
+        return inits, hos, self.ctx.population_read_crash(rows)[0] if self.adv.model.family == "crash" else None
+
+    def advance(self, elite, parents, n_fresh, generation):
+        P, ne, nm = self.adv.population, len(elite), len(parents)
+        parent = np.zeros(P, np.uint32)
+        op = np.full(P, 2, np.uint8)  # 0: copy, 1: mutate, 2: fresh
+        parent[:ne], op[:ne] = elite, 0
+        parent[ne:ne + nm], op[ne:ne + nm] = parents, 1
+        t = time.perf_counter()
+        if self.pm is None:
+            self.ctx.population_next(parent, op, self._params(generation))
+        else:
+            self.ctx.population_next_model(parent, op, self._params(generation), self.pm)
+        return time.perf_counter() - t
 
 
 class Adversary:
@@ -202,7 +329,7 @@ class Adversary:
         self.device_pop = device_pop
         self.device_models = device_models
         self.device_shrink = device_shrink
-        self.shrink_stats = {"steps": 0, "batches": 0, "candidates": 0}  # of the last shrink_device call
+        self.shrink_stats = {"steps": 0, "batches": 0, "candidates": 0}  # of the last shrink / shrink_device call
         self.rng = np.random.default_rng(seed)
         self._own = evaluator is None
         self.evaluator = evaluator or GpuEvaluator(alg, n, rounds, population, device=device,
@@ -223,16 +350,18 @@ class Adversary:
     def _fresh(self, I):
         m, n, R = self.model, self.n, self.R
         if m.family == "crash":
-            crash, partial = S.random_crash(self.rng, I, R, n, m.fmax, p_partial=(0.05, 0.15, 0.5, 0.85))
+            crash, partial = S.random_crash(self.rng, I, R, n, m.fmax, p_partial=CRASH_DELIVERY)
             return {"crash": crash, "partial": partial}
         # a spread of loss rates around `keep` (each quarter of the population its own)
         parts = []
-        levels = [min(0.97, self.keep * f) for f in (0.7, 0.85, 1.0, 1.15)]
-        for j, kp in enumerate(levels):
+        for j, kp in enumerate(self._keep_levels()):
             m = I // 4 + (1 if j < I % 4 else 0)
             if m:
                 parts.append(S.random_omission(self.rng, m, R, n, kp, self.self_bit))
         return {"ho": np.concatenate(parts)}
+
+    def _keep_levels(self):
+        return [min(0.97, self.keep * f) for f in LOSS_SPREAD]
 
     def _realize(self, g):
         """Genome -> (ho, crash, valid): HO sets repaired to the model's constraints;
@@ -281,7 +410,7 @@ class Adversary:
     def _mutate(self, g, strength):
         m = self.model
         if m.family == "crash":
-            c, p = S.mutate_crash(g["crash"], g["partial"], self.rng, self.R, self.n, m.fmax)
+            c, p = S.mutate_crash(g["crash"], g["partial"], self.rng, self.R, self.n, m.fmax, CRASH_MUTATE)
             return {"crash": c, "partial": p}
         ho = g["ho"].copy()
         S.flip_links(ho, self.rng, self.n, strength, self.self_bit)
@@ -354,9 +483,9 @@ class Adversary:
         pm = abi.PopulationModel()
         if m.family == "crash":
             pm.family, pm.fmax = abi.PSG_POP_CRASH, m.fmax
-            for j, d in enumerate((0.05, 0.15, 0.5, 0.85)):  # the host generator's delivery densities
-                pm.partial_p256[j] = int(round(d * 256))
-            pm.move_p256, pm.add_p256, pm.drop_p256 = 77, 77, 38  # schedules.mutate_crash: 0.3, 0.3, 0.15
+            for j, d in enumerate(CRASH_DELIVERY):
+                pm.partial_p256[j] = _p256(d)
+            pm.move_p256, pm.add_p256, pm.drop_p256 = _p256(CRASH_MUTATE), _p256(CRASH_MUTATE), _p256(CRASH_MUTATE / 2)
             return pm
         pm.family = abi.PSG_POP_OMISSION
         pm.live_kind = LIVE_KIND[m.liveness]
@@ -366,59 +495,29 @@ class Adversary:
         pm.phase, pm.coord = m.phase, m.coord
         return pm
 
-    def _pop_params(self, generation):
-        p = abi.PopulationParams()
-        p.seed = int(self.rng.integers(0, 1 << 63)) if generation == 0 else self._pop_seed
-        if generation == 0:
-            self._pop_seed = p.seed
-        p.generation = generation
-        # (crash family: one crash-round delivery toggled per mutant, as schedules.mutate_crash)
-        p.flips = 1 if self.model.family == "crash" else max(1, int(self.n * self.R * 0.01))
-        p.min_size = self.model.min_size or 0
-        p.self_bit = 1 if self.self_bit else 0
-        for j, f in enumerate((0.7, 0.85, 1.0, 1.15)):  # the host generator's spread of loss rates
-            p.keep_p256[j] = int(round(min(0.97, self.keep * f) * 256))
-        p.value_range = self.values
-        p.redraw_p256 = 5  # ~2 % of a mutant's initial values redrawn
-        return p
-
-    def _search_device(self, generations, want, time_budget, elite_frac, fresh_frac, shrink):
-        """The search loop with the population resident in HBM: per generation one
-        psg_run_batch, the per-instance summaries + decisions to the host for scoring,
-        and psg_population_next with the chosen parents (no HO set crosses PCIe)."""
+    def search(self, generations: int = 50, want: int = 1, time_budget: Optional[float] = None,
+               elite_frac: float = 0.25, fresh_frac: float = 0.25, shrink: bool = True) -> SearchResult:
+        """The search loop: evaluate the population, collect genuine violations, score, and build
+        the next generation from elites, mutants of elites and fresh schedules."""
         P = self.population
-        ctx = self.evaluator.gr._ctx
-        base = self.next_id
-        self.next_id += P
-        pm = self._pop_model()
-        if pm is None:
-            ctx.population_fresh(base, P, self._pop_params(0))
-        else:
-            ctx.population_fresh_model(base, P, self._pop_params(0), pm)
+        pop = _DevicePopulation(self) if self.device_population() else _HostPopulation(self)
+        pop.fresh()
         found: List[Counterexample] = []
         t0 = time.perf_counter()
         gpu = 0.0
         history = []
         g = 0
         for g in range(1, generations + 1):
-            t1 = time.perf_counter()
-            _, pi = ctx.run_batch_np(base, P)
-            dec, dr = ctx.copy_decisions_np()
-            gpu += time.perf_counter() - t1
-            ev = Eval(pi, dec, dr)
+            ev, valid, t = pop.evaluate()
+            gpu += t
             bad, first = self._violations(ev)
-            if self.mode == "liveness":  # only instances with enough live rounds count (the host loop's `valid`)
-                t1 = time.perf_counter()
-                live = ctx.population_live(pm.live_kind, pm.phase, pm.coord)
-                gpu += time.perf_counter() - t1
-                bad &= live.sum(1) >= self.live_rounds
+            bad &= valid
             rows = np.nonzero(bad)[0][:max(0, want - len(found))]
             if len(rows):
-                hos, inits = ctx.population_read(rows)
-                crashes = ctx.population_read_crash(rows)[0] if self.model.family == "crash" else None
+                inits, hos, crashes = pop.read(rows)
                 for j, i in enumerate(rows):
-                    found.append(self._cex(base + int(i), inits[j], hos[j], None if crashes is None else crashes[j],
-                                           pi[i], int(first[i])))
+                    found.append(self._cex(pop.base + int(i), inits[j], hos[j], None if crashes is None else crashes[j],
+                                           ev.summary[i], int(first[i])))
             score = self._score(ev)
             history.append(float(score.max()))
             if len(found) >= want or (time_budget is not None and time.perf_counter() - t0 > time_budget):
@@ -428,71 +527,11 @@ class Adversary:
             nf = int(P * fresh_frac)
             nm = P - ne - nf
             elite = order[:ne]
-            parent = np.zeros(P, np.uint32)
-            op = np.full(P, 2, np.uint8)
-            parent[:ne], op[:ne] = elite, 0
-            parent[ne:ne + nm], op[ne:ne + nm] = elite[self.rng.integers(0, ne, nm)], 1
-            t1 = time.perf_counter()
-            if pm is None:
-                ctx.population_next(parent, op, self._pop_params(g))
-            else:
-                ctx.population_next_model(parent, op, self._pop_params(g), pm)
-            gpu += time.perf_counter() - t1
+            gpu += pop.advance(elite, elite[self.rng.integers(0, ne, nm)], nf, g)
         secs = time.perf_counter() - t0
         if shrink:
             found = [self._shrink(c) for c in found]
         return SearchResult(found, P * g, g, secs, gpu, history)
-
-    def search(self, generations: int = 50, want: int = 1, time_budget: Optional[float] = None,
-               elite_frac: float = 0.25, fresh_frac: float = 0.25, shrink: bool = True) -> SearchResult:
-        if self.device_population():
-            return self._search_device(generations, want, time_budget, elite_frac, fresh_frac, shrink)
-        P = self.population
-        genome = self._fresh(P)
-        init = default_init(self.alg, self.rng, P, self.n, self.values)
-        found: List[Counterexample] = []
-        t0 = time.perf_counter()
-        gpu = 0.0
-        evaluated = 0
-        history = []
-        g = 0
-        for g in range(1, generations + 1):
-            ho, crash, valid = self._realize(genome)
-            base = self.next_id
-            self.next_id += P
-            t1 = time.perf_counter()
-            ev = self.evaluator(base, ho, crash, init)
-            gpu += time.perf_counter() - t1
-            evaluated += P
-            bad, first = self._violations(ev)
-            bad &= valid
-            for i in np.nonzero(bad)[0][:max(0, want - len(found))]:
-                found.append(self._cex(base + int(i), init[i], ho[i], None if crash is None else crash[i],
-                                       ev.summary[i], int(first[i])))
-            score = self._score(ev)
-            history.append(float(score.max()))
-            if len(found) >= want or (time_budget is not None and time.perf_counter() - t0 > time_budget):
-                break
-            # next generation: elites + mutants of elites + fresh schedules
-            order = np.argsort(-score)
-            ne = max(1, int(P * elite_frac))
-            nf = int(P * fresh_frac)
-            nm = P - ne - nf
-            elite = order[:ne]
-            parents = elite[self.rng.integers(0, ne, nm)]
-            strength = max(1, int(self.n * self.R * 0.01))
-            children = self._mutate(self._take(genome, parents), strength)
-            genome = self._cat(self._cat(self._take(genome, elite), children), self._fresh(nf)) if nf else \
-                self._cat(self._take(genome, elite), children)
-            cinit = init[parents].copy()
-            flip = self.rng.random(cinit.shape) < 0.02
-            fresh_init = default_init(self.alg, self.rng, cinit.shape[0], self.n, self.values)
-            cinit[flip] = fresh_init[flip]
-            init = np.concatenate([init[elite], cinit, default_init(self.alg, self.rng, nf, self.n, self.values)])
-        secs = time.perf_counter() - t0
-        if shrink:
-            found = [self._shrink(c) for c in found]
-        return SearchResult(found, evaluated, g, secs, gpu, history)
 
     def _cex(self, inst, init, ho, crash, summ, first):
         ff = summ["first_fail"]
@@ -515,27 +554,21 @@ class Adversary:
         """Evaluate candidate schedules of counterexample c (same init and instance id)."""
         I = hos.shape[0]
         init = np.repeat(c.init[None], I, 0)
-        out_bad = np.zeros(I, bool)
-        out_first = np.full(I, NEVER, np.int32)
-        out_sum = None
-        cap = self.population
-        sums = []
-        for a in range(0, I, cap):
-            b = min(I, a + cap)
+        bads, firsts, sums = [], [], []
+        for a in range(0, I, self.population):
+            b = min(I, a + self.population)
             # every candidate replays the counterexample's own instance id (same coins)
             ev = self._eval_same_id(c.inst_id, hos[a:b], None if crashes is None else crashes[a:b], init[a:b])
             bad, first = self._violations(ev)
-            out_bad[a:b], out_first[a:b] = bad, first
+            bads.append(bad)
+            firsts.append(first)
             sums.append(ev.summary)
-        out_sum = np.concatenate(sums)
-        return out_bad, out_first, out_sum
+        return np.concatenate(bads), np.concatenate(firsts), np.concatenate(sums)
 
     def _eval_same_id(self, inst, ho, crash, init):
-        """Instances share an id only through separate batches; BenOr's coin depends on
-        the id, so candidates run one id each: ids inst, inst+1, ... would change
-        coins. Run each candidate as its own instance id `inst` in chunks of one
-        contiguous batch per distinct id is too slow, so coins are id-keyed only for
-        BenOr: other algorithms are id-independent under an explicit schedule."""
+        """BenOr's coins are keyed by the instance id, so its candidates run one per call under
+        the counterexample's id. Other algorithms do not depend on the id under an explicit
+        schedule, so they run as one batch."""
         if self.alg.alg_id != abi.PSG_ALG_BENOR:
             return self.evaluator(inst, ho, crash, init)
         outs = [self.evaluator(inst, ho[j:j + 1], None if crash is None else crash[j:j + 1], init[j:j + 1])
@@ -543,108 +576,108 @@ class Adversary:
         return Eval(np.concatenate([o.summary for o in outs]), np.concatenate([o.decision for o in outs]),
                     np.concatenate([o.decision_round for o in outs]))
 
-    def shrink(self, c: Counterexample, max_steps: int = 64) -> Counterexample:
-        """Greedy batched delta debugging: restore omitted links (whole rounds, then
-        whole heard-of sets, then single links; crash-stop: un-crash processes,
-        deliver crash-round messages) while the violation persists, and make the
-        rounds after the violation fault-free."""
-        n, R = self.n, self.R
-        fm = S.full_mask(n)
-        ho = c.ho.copy()
-        crash = None if c.crash is None else c.crash.copy()
+    def _shrink_plan(self, c: Counterexample, max_steps, step) -> Counterexample:
+        """Greedy batched delta debugging, the plan of both paths. step(cur, level, arg) evaluates
+        the candidates of one abi.PSG_SHRINK_* level over the current counterexample and returns
+        the one it adopted, or None (no candidate, or none still bad). Crash-stop: un-crash
+        processes and crash them later (CRASH, arg = the self bit) while that succeeds. Omission:
+        make the rounds after the violation fault-free (TAIL, not counted as a step), then restore
+        whole rounds, whole heard-of sets and single links (LINK: at most about 4 * population
+        candidates); restoring links only grows HO sets, so the model's predicates keep holding.
+        The levels share the budget of max_steps, and a level ends with its first step that
+        adopts nothing. Fills shrink_stats."""
+        self.shrink_stats = stats = {"steps": 0, "batches": 0, "candidates": 0}
         cur = c
-        steps = 0
 
-        def accept(cands_ho, cands_crash):
-            nonlocal ho, crash, cur
-            bad, first, summ = self._still_bad(cur, cands_ho, cands_crash)
-            if not bad.any():
-                return False
-            # prefer the simplest candidate: most links present, then earliest violation
-            links = S.sizes(cands_ho).sum((-1, -2))
-            key = np.where(bad, links * 1024 - first, -1)
-            j = int(np.argmax(key))
-            ho = cands_ho[j].copy()
-            crash = None if cands_crash is None else cands_crash[j].copy()
-            viol = cur.violated if self.mode == "liveness" else \
-                [self.names[t] for t in self.targets if summ[j]["first_fail"][t] == first[j]]
-            cur = Counterexample(cur.inst_id, cur.init, ho.copy(), None if crash is None else crash.copy(),
-                                 summ[j], viol, int(first[j]), self._omitted(ho))
-            return True
+        def once(level, arg):
+            nonlocal cur
+            nxt = step(cur, level, arg)
+            if nxt is not None:
+                cur = nxt
+            return nxt is not None
+
+        def repeat(level, arg):
+            while stats["steps"] < max_steps:
+                stats["steps"] += 1
+                if not once(level, arg):
+                    break
 
         if self.model.family == "crash":
-            while steps < max_steps:
-                steps += 1
-                cands_c, cands_h = [], []
-                for q in np.nonzero(crash >= 0)[0]:          # un-crash q
-                    cc = crash.copy()
-                    cc[q] = -1
-                    cands_c.append(cc)
-                for q in np.nonzero(crash >= 0)[0]:          # crash q later
-                    if crash[q] + 1 < R:
-                        cc = crash.copy()
-                        cc[q] += 1
-                        cands_c.append(cc)
-                if not cands_c:
-                    break
-                cc = np.stack(cands_c)
-                # keep the crash-round deliveries of the current schedule
-                part = np.zeros((len(cands_c), n, S.words(n)), np.uint64)
-                for q in range(n):
-                    if crash[q] >= 0:
-                        row = ho[crash[q]]  # [n][W]: who hears q in q's crash round
-                        part[:, :, q >> 6] |= row[:, q >> 6] & np.uint64(1 << (q & 63))
-                hh = S.crash_to_ho(cc, part, R, n, self.self_bit)
-                if not accept(hh, cc):
-                    break
+            repeat(abi.PSG_SHRINK_CRASH, 1 if self.self_bit else 0)
             return cur
-
-        if self.mode == "safety" and cur.check_point < NEVER:
-            # rounds after the violating check point are irrelevant: fault-free
-            h2 = ho.copy()
-            h2[cur.check_point:] = fm
-            accept(h2[None], None)
-        # predicate-preserving: restoring links only grows HO sets, so |HO(p)| >= m and
-        # good rounds (if |s| grows uniformly) stay; liveness keeps its forced rounds
-        for level in ("round", "set", "link"):
-            while steps < max_steps:
-                steps += 1
-                cands = []
-                if level == "round":
-                    for k in range(R):
-                        if (ho[k] != fm).any():
-                            h2 = ho.copy()
-                            h2[k] = fm
-                            cands.append(h2)
-                elif level == "set":
-                    for k in range(R):
-                        for p in range(n):
-                            if (ho[k, p] != fm).any():
-                                h2 = ho.copy()
-                                h2[k, p] = fm
-                                cands.append(h2)
-                else:
-                    for k in range(R):
-                        for p in range(n):
-                            miss = [q for q in range(n) if not (int(ho[k, p, q >> 6]) >> (q & 63)) & 1]
-                            for q in miss:
-                                h2 = ho.copy()
-                                h2[k, p, q >> 6] |= np.uint64(1 << (q & 63))
-                                cands.append(h2)
-                            if len(cands) > 4 * self.population:
-                                break
-                        if len(cands) > 4 * self.population:
-                            break
-                if not cands:
-                    break
-                hh = np.stack(cands)
-                if self.mode == "liveness":
-                    hh = hh[self._live_count(hh) >= self.live_rounds]
-                    if not len(hh):
-                        break
-                if not accept(hh, None):
-                    break
+        if self.mode == "safety" and c.check_point < NEVER:
+            once(abi.PSG_SHRINK_TAIL, c.check_point)
+        repeat(abi.PSG_SHRINK_ROUND, 0)
+        repeat(abi.PSG_SHRINK_SET, 0)
+        repeat(abi.PSG_SHRINK_LINK, 4 * self.population)
         return cur
+
+    @staticmethod
+    def _simplest(bad, first, links, valid=None):
+        """The selection rule of a shrink step: among the candidates still bad the one with the
+        most links present, then the earliest violation; the first one of several. (key, index);
+        candidates that are not `valid` rank below every other."""
+        key = np.where(bad, links.astype(np.int64) * 1024 - first, -1)
+        if valid is not None:
+            key[~valid] = np.iinfo(np.int64).min
+        j = int(np.argmax(key))
+        return int(key[j]), j
+
+    def _adopted(self, cur: Counterexample, summ, first, **fields) -> Counterexample:
+        """cur after a step chose the candidate with this summary and first violating check point."""
+        viol = cur.violated if self.mode == "liveness" else \
+            [self.names[t] for t in self.targets if summ["first_fail"][t] == first]
+        return replace(cur, summary=summ, violated=viol, check_point=int(first), **fields)
+
+    def _shrink_step_host(self, cur: Counterexample, level, arg) -> Optional[Counterexample]:
+        """One step with the candidates built and uploaded by the host, in chunks of `population`."""
+        hos, crashes = S.shrink_candidates(cur.ho, cur.crash, level, arg, self.n, self.self_bit)
+        if len(hos) and self.mode == "liveness":
+            assert crashes is None  # (liveness models are of the omission family: no crash rounds to filter along)
+            hos = hos[self._live_count(hos) >= self.live_rounds]
+        if not len(hos):
+            return None
+        bad, first, summ = self._still_bad(cur, hos, crashes)
+        self.shrink_stats["batches"] += 1
+        self.shrink_stats["candidates"] += len(hos)
+        if not bad.any():
+            return None
+        _, j = self._simplest(bad, first, S.sizes(hos).sum((-1, -2)))
+        return self._adopted(cur, summ[j], first[j], ho=hos[j].copy(),
+                             crash=None if crashes is None else crashes[j].copy(), omitted_links=self._omitted(hos[j]))
+
+    def _shrink_step_device(self, cur: Counterexample, level, arg) -> Optional[Counterexample]:
+        """One step with the candidates written on the device (psg_shrink_load) over the base
+        resident there; per chunk of `population` candidates only the summaries, the link counts
+        and (liveness) the live rounds come to the host. cur keeps the ho / crash / omitted_links
+        it came with: shrink_device reads them once, at the end."""
+        ctx, m, P = self.evaluator.gr._ctx, self.model, self.population
+        total = ctx.shrink_count(level, arg)
+        self.shrink_stats["batches"] += int(total > 0)
+        best = (np.iinfo(np.int64).min,)  # (key, index, summary, first) of the first maximum so far
+        any_bad = False
+        for a in range(0, total, P):
+            k = min(P, total - a)
+            ctx.shrink_load(level, arg, a, k, cur.inst_id)  # every candidate replays the counterexample's id
+            _, pi = ctx.run_batch_np(cur.inst_id, k)
+            self.shrink_stats["candidates"] += k
+            bad, first = self._violations(Eval(pi, None, None))
+            links, valid = ctx.population_links(), None
+            if self.mode == "liveness":  # the host drops these candidates before it evaluates
+                valid = ctx.population_live(LIVE_KIND[m.liveness], m.phase, m.coord).sum(1) >= self.live_rounds
+                bad &= valid
+            any_bad |= bool(bad.any())
+            key, j = self._simplest(bad, first, links, valid)
+            if key > best[0]:
+                best = (key, a + j, pi[j].copy(), int(first[j]))
+        if not any_bad:
+            return None
+        ctx.shrink_adopt(level, arg, best[1])
+        return self._adopted(cur, best[2], best[3])
+
+    def shrink(self, c: Counterexample, max_steps: int = 64) -> Counterexample:
+        """Shrink c while the violation persists (_shrink_plan), the candidates built on the host."""
+        return self._shrink_plan(c, max_steps, self._shrink_step_host)
 
     def _shrink(self, c: Counterexample) -> Counterexample:
         """search(shrink=True): on the device when device_shrink is set and available."""
@@ -659,78 +692,21 @@ class Adversary:
             self.alg.alg_id != abi.PSG_ALG_BENOR
 
     def shrink_device(self, c: Counterexample, max_steps: int = 64) -> Counterexample:
-        """shrink() with the candidates of every step written on the device (psg_shrink_load) from
-        a base schedule resident there: the same levels, candidate order, cap, step accounting and
-        selection, so the same counterexample bit for bit. Per chunk of `population` candidates
-        only the per-instance summaries, the link counts and (liveness) the live rounds come to
-        the host; the HO sets come once, at the end. In liveness mode every candidate of a list is
-        evaluated and the ones with too few live rounds are then left out of the choice, where the
-        host drops them before it evaluates: shrink_stats["candidates"] counts them, so it can
-        exceed the host's count (the result does not change)."""
+        """shrink() with the candidates of every step written on the device from a base schedule
+        resident there: the same plan and selection, so the same counterexample bit for bit. In
+        liveness mode every candidate of a list is evaluated and the ones with too few live rounds
+        are then left out of the choice, where the host drops them before it evaluates:
+        shrink_stats["candidates"] counts them, so it can exceed the host's count (the result does
+        not change)."""
         if not self.device_shrink_available():
             raise ValueError("shrink_device needs the GPU evaluator, integer inputs and an algorithm other than BenOr")
         ctx = self.evaluator.gr._ctx
-        m, P = self.model, self.population
         ctx.shrink_begin(c.ho, c.crash, c.init)
-        cur = c           # (its ho / crash / omitted_links are filled in from the device at the end)
-        accepted = False
-        steps = batches = evaluated = 0
-        lowest = np.iinfo(np.int64).min
-
-        def step(level, arg):
-            """One batch of candidates over the base; adopts the host's choice. False: no candidate
-            (left after the liveness filter) or none still bad."""
-            nonlocal cur, accepted, batches, evaluated
-            total = ctx.shrink_count(level, arg)
-            batches += total > 0
-            best = None  # (key, index, summary, first) of the first maximum so far
-            any_bad = False
-            for a in range(0, total, P):
-                k = min(P, total - a)
-                ctx.shrink_load(level, arg, a, k, cur.inst_id)  # every candidate replays the counterexample's id
-                _, pi = ctx.run_batch_np(cur.inst_id, k)
-                evaluated += k
-                bad, first = self._violations(Eval(pi, None, None))
-                links = ctx.population_links().astype(np.int64)
-                key = np.where(bad, links * 1024 - first, -1)
-                if self.mode == "liveness":  # the host drops these candidates before it evaluates
-                    live = ctx.population_live(LIVE_KIND[m.liveness], m.phase, m.coord)
-                    valid = live.sum(1) >= self.live_rounds
-                    bad &= valid
-                    key[~valid] = lowest
-                any_bad |= bool(bad.any())
-                j = int(np.argmax(key))
-                if key[j] > (lowest if best is None else best[0]):
-                    best = (int(key[j]), a + j, pi[j].copy(), int(first[j]))
-            if not any_bad:
-                return False
-            _, j, summ, first = best
-            ctx.shrink_adopt(level, arg, j)
-            viol = cur.violated if self.mode == "liveness" else \
-                [self.names[t] for t in self.targets if summ["first_fail"][t] == first]
-            cur = Counterexample(cur.inst_id, cur.init, cur.ho, cur.crash, summ, viol, first, cur.omitted_links)
-            accepted = True
-            return True
-
-        if m.family == "crash":
-            while steps < max_steps:
-                steps += 1
-                if not step(abi.PSG_SHRINK_CRASH, 1 if self.self_bit else 0):
-                    break
-        else:
-            if self.mode == "safety" and cur.check_point < NEVER:
-                step(abi.PSG_SHRINK_TAIL, cur.check_point)
-            for level, arg in ((abi.PSG_SHRINK_ROUND, 0), (abi.PSG_SHRINK_SET, 0), (abi.PSG_SHRINK_LINK, 4 * P)):
-                while steps < max_steps:
-                    steps += 1
-                    if not step(level, arg):
-                        break
-        self.shrink_stats = {"steps": steps, "batches": batches, "candidates": evaluated}
-        if not accepted:
+        cur = self._shrink_plan(c, max_steps, self._shrink_step_device)
+        if cur is c:  # nothing adopted
             return c
         ho, crash = ctx.shrink_read()
-        return Counterexample(cur.inst_id, cur.init, ho, crash, cur.summary, cur.violated, cur.check_point,
-                              self._omitted(ho))
+        return replace(cur, ho=ho, crash=crash, omitted_links=self._omitted(ho))
 
 
 # ------------------------------------------------------------------ files

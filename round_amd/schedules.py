@@ -29,6 +29,8 @@ from typing import Optional
 
 import numpy as np
 
+from . import abi
+
 U64 = np.uint64
 ALL = np.uint64(0xFFFFFFFFFFFFFFFF)
 
@@ -203,6 +205,58 @@ def crash_to_ho(crash: np.ndarray, partial: np.ndarray, R: int, n: int, self_bit
         c = (now[:, :, None] * bit[None]).sum(1, dtype=U64)     # [I][W]
         ho[:, k] = a[:, None, :] | (c[:, None, :] & partial)
     return apply_universe(ho, n, self_bit)
+
+
+def shrink_candidates(ho: np.ndarray, crash: Optional[np.ndarray], level: int, arg: int, n: int,
+                      self_bit: bool = True):
+    """The candidate simplifications of one shrink step over the base (ho [R][n][W], crash [n] or
+    None), in the order psg_shrink_* enumerates them: (hos [K][R][n][W], crashes [K][n] or None).
+      TAIL   the rounds from check point `arg` on fault-free (one candidate)
+      ROUND  one round with an omission made fault-free, per such round
+      SET    one heard-of set with an omission made full, per such (round, process)
+      LINK   one omitted link restored, per (round, process, sender); with arg > 0 the list ends
+             with the first heard-of set that brings it above arg candidates
+      CRASH  one crashed process un-crashed, per such process, then one crash a round later, per
+             process crashed before the last round; the crash-round deliveries stay the base's
+    Below CRASH every candidate keeps the base's crash rounds."""
+    R, fm = ho.shape[0], full_mask(n)
+
+    def restored(*where):  # one candidate per index tuple, that part of it set to all processes
+        out = np.repeat(ho[None], len(where[0]), 0)
+        out[(np.arange(len(out)),) + where] = fm
+        return out
+
+    if level == abi.PSG_SHRINK_CRASH:
+        crashed = np.nonzero(crash >= 0)[0]
+        later = crashed[crash[crashed] + 1 < R]
+        cc = np.repeat(crash[None], len(crashed) + len(later), 0)
+        cc[np.arange(len(crashed)), crashed] = -1
+        cc[len(crashed) + np.arange(len(later)), later] += 1
+        part = np.zeros((n, words(n)), U64)
+        for q in map(int, crashed):  # who hears q in q's crash round
+            part[:, q >> 6] |= ho[crash[q], :, q >> 6] & np.uint64(1 << (q & 63))
+        return crash_to_ho(cc, np.repeat(part[None], len(cc), 0), R, n, self_bit), cc
+    if level == abi.PSG_SHRINK_TAIL:
+        hos = ho.copy()[None]
+        hos[0, arg:] = fm
+    elif level == abi.PSG_SHRINK_ROUND:
+        hos = restored(np.nonzero((ho != fm).any((1, 2)))[0])
+    elif level == abi.PSG_SHRINK_SET:
+        hos = restored(*np.nonzero((ho != fm).any(2)))
+    elif level == abi.PSG_SHRINK_LINK:
+        q = np.arange(n)
+        present = (ho[:, :, q >> 6] >> (q & 63).astype(U64)) & U64(1)   # [R][n][n]
+        k, p, q = np.nonzero(present == 0)
+        if arg:
+            upto = np.cumsum((present == 0).sum(2).reshape(-1))  # candidates up to and including each set
+            over = np.nonzero(upto > arg)[0]
+            if len(over):
+                k, p, q = k[:upto[over[0]]], p[:upto[over[0]]], q[:upto[over[0]]]
+        hos = np.repeat(ho[None], len(k), 0)
+        hos[np.arange(len(k)), k, p, q >> 6] |= U64(1) << (q & 63).astype(U64)
+    else:
+        raise ValueError(f"unknown shrink level {level}")
+    return hos, None if crash is None else np.repeat(crash[None], len(hos), 0)
 
 
 # ------------------------------------------------------------------ repair and mutation

@@ -65,13 +65,6 @@ def model_rows(population, generations, device_models, **extra):
     return out
 
 
-def same_counterexample(a, b):
-    return ((a.ho == b.ho).all() and (a.crash is None) == (b.crash is None)
-            and (a.crash is None or (a.crash == b.crash).all()) and a.check_point == b.check_point
-            and a.violated == b.violated and a.omitted_links == b.omitted_links
-            and bytes(a.summary.tobytes()) == bytes(b.summary.tobytes()))
-
-
 def shrink_rows(name, alg, n, R, passes, max_steps, population, generations=60, **kw):
     """One counterexample found with shrink=False, then `passes` passes alternating Adversary.shrink
     (the host builds and uploads every candidate) and Adversary.shrink_device (psg_shrink_*) on it,
@@ -84,25 +77,15 @@ def shrink_rows(name, alg, n, R, passes, max_steps, population, generations=60, 
         if not res.counterexamples:
             raise SystemExit(f"{name}: no counterexample in {res.schedules_evaluated} schedules")
         c = res.counterexamples[0]
-        counted = {"batches": 0, "candidates": 0}
-        still_bad = adv._still_bad
-
-        def counting(cur, hos, crashes):
-            counted["batches"] += 1
-            counted["candidates"] += int(hos.shape[0])
-            return still_bad(cur, hos, crashes)
-
-        adv._still_bad = counting
 
         def one(path, k):
-            counted.update(batches=0, candidates=0)
             t0 = time.perf_counter()
             out = adv.shrink(c, max_steps) if path == "host" else adv.shrink_device(c, max_steps)
             secs = time.perf_counter() - t0
-            stats = dict(counted) if path == "host" else adv.shrink_stats
+            stats = adv.shrink_stats
             return out, {"row": name, "path": path, "pass": k, "n": n, "rounds": R, "population": population,
                          "max_steps": max_steps, "seconds": round(secs, 4), "batches": stats["batches"],
-                         "steps": stats.get("steps"), "candidates": stats["candidates"],
+                         "steps": stats["steps"], "candidates": stats["candidates"],
                          "omitted_links_before": int(c.omitted_links), "omitted_links_after": int(out.omitted_links)}
 
         one("host", -1)
@@ -110,7 +93,7 @@ def shrink_rows(name, alg, n, R, passes, max_steps, population, generations=60, 
         for k in range(passes):
             host, hrow = one("host", k)
             dev, drow = one("device", k)
-            hrow["identical"] = drow["identical"] = bool(same_counterexample(host, dev))
+            hrow["identical"] = drow["identical"] = host.same(dev)
             for r in (hrow, drow):
                 print(json.dumps(r), flush=True)
             rows += [hrow, drow]

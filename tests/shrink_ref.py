@@ -75,7 +75,4 @@ def candidates(ho, crash, level, arg, n, R, self_bit=True):
 
 def same_cex(a, b):
     """Two adversary.Counterexample are the same, bit for bit."""
-    return (a.inst_id == b.inst_id and (a.ho == b.ho).all() and (a.init == b.init).all()
-            and (a.crash is None) == (b.crash is None) and (a.crash is None or (a.crash == b.crash).all())
-            and a.check_point == b.check_point and a.violated == b.violated and a.omitted_links == b.omitted_links
-            and np.asarray(a.summary).tobytes() == np.asarray(b.summary).tobytes())
+    return a.same(b)

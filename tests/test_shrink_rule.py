@@ -1,10 +1,9 @@
 """Shrinking on the device, the CPU side: the restatement of the candidate lists (tests/shrink_ref.py,
 what psg_shrink_* is tested against on the GPU) is pinned to the batches Adversary.shrink really
-evaluates; the device_shrink switch falls back to shrink() without the GPU evaluator; the enum and
-the exports of the C ABI."""
+evaluates and to schedules.shrink_candidates, which builds them; the device_shrink switch falls
+back to shrink() without the GPU evaluator; the enum and the exports of the C ABI."""
 import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -43,6 +42,19 @@ CASES = [
 ]
 
 
+def _same_lists(ho, crash, cp, cap, n, R, self_bit):
+    """schedules.shrink_candidates, the list function of the host step, is the restatement: every
+    level over this base, LINK with and without the cap."""
+    cases = [(abi.PSG_SHRINK_TAIL, cp), (abi.PSG_SHRINK_ROUND, 0), (abi.PSG_SHRINK_SET, 0), (abi.PSG_SHRINK_LINK, 0),
+             (abi.PSG_SHRINK_LINK, cap)] + ([] if crash is None else [(abi.PSG_SHRINK_CRASH, 0)])
+    for level, arg in cases:
+        want_ho, want_cr = candidates(ho, crash, level, arg, n, R, self_bit)
+        got_ho, got_cr = S.shrink_candidates(ho, crash, level, arg, n, self_bit)
+        assert got_ho.shape == want_ho.shape and got_ho.dtype == want_ho.dtype and (got_ho == want_ho).all(), level
+        assert (got_cr is None) == (crash is None), level
+        assert crash is None or (got_cr.dtype == want_cr.dtype and (got_cr == want_cr).all()), level
+
+
 @pytest.mark.parametrize("name,alg,n,R,P,V,mode,kw", CASES, ids=[c[0] for c in CASES])
 def test_restatement_is_what_shrink_evaluates(name, alg, n, R, P, V, mode, kw, oracle_mod):
     rec = Recorder(OracleEvaluator(alg, n, R, value_range=V))
@@ -50,34 +62,35 @@ def test_restatement_is_what_shrink_evaluates(name, alg, n, R, P, V, mode, kw, o
     res = adv.search(generations=40, want=1, shrink=False)
     assert res.counterexamples, name
     c0 = res.counterexamples[0]
-    steps = []  # (base ho, base crash, check point of the base, first recorded call, level) of the step
-    still_bad = adv._still_bad
-    names = {"round": abi.PSG_SHRINK_ROUND, "set": abi.PSG_SHRINK_SET, "link": abi.PSG_SHRINK_LINK}
+    steps = []  # (base ho, base crash, check point of the base, first recorded call, level, arg) of the step
+    host_step = adv._shrink_step_host
 
-    def marking(c, hos, crashes):
-        # the level is shrink()'s own: the loop variable of the frame that called accept() (before
-        # the loop: the tail step; the crash family has one level)
-        loop = sys._getframe(2)
-        assert loop.f_code is A.Adversary.shrink.__code__
-        level = abi.PSG_SHRINK_CRASH if adv.model.family == "crash" else \
-            names[loop.f_locals["level"]] if "level" in loop.f_locals else abi.PSG_SHRINK_TAIL
-        steps.append((c.ho.copy(), None if c.crash is None else c.crash.copy(), c.check_point, len(rec.calls), level))
-        return still_bad(c, hos, crashes)
+    def marking(cur, level, arg):  # the level and its argument are the ones the shrink plan hands to the step
+        steps.append((cur.ho.copy(), None if cur.crash is None else cur.crash.copy(), cur.check_point, len(rec.calls),
+                      level, arg))
+        return host_step(cur, level, arg)
 
-    adv._still_bad = marking
+    adv._shrink_step_host = marking
     rec.calls.clear()
     c1 = adv.shrink(c0)
     assert steps and not same_cex(c0, c1), f"{name}: shrink() left the counterexample unchanged"
+    assert [s[4] for s in steps] == sorted(s[4] for s in steps)  # (the steps that found nothing to evaluate included)
     bounds = [s[3] for s in steps] + [len(rec.calls)]
     level_at, truncated = [], 0
-    for (ho, crash, cp, a, level), b in zip(steps, bounds[1:]):
+    for (ho, crash, cp, a, level, got_arg), b in zip(steps, bounds[1:]):
+        arg = {abi.PSG_SHRINK_TAIL: cp, abi.PSG_SHRINK_LINK: 4 * P}.get(level, 0)
+        assert got_arg == (int(adv.self_bit) if level == abi.PSG_SHRINK_CRASH else arg), (name, level, got_arg)
+        assert (level == abi.PSG_SHRINK_CRASH) == (adv.model.family == "crash")
+        want_ho, want_cr = candidates(ho, crash, level, arg, n, R, adv.self_bit)
+        _same_lists(ho, crash, cp, 4 * P, n, R, adv.self_bit)
+        if mode == "liveness":  # the host drops candidates with too few live rounds before it evaluates
+            want_ho = want_ho[adv._live_count(want_ho) >= adv.live_rounds]
+        if a == b:  # the step evaluated nothing: its list was empty (the step that ends a level)
+            assert len(want_ho) == 0, (name, len(level_at), level)
+            continue
         got_ho = np.concatenate([x[0] for x in rec.calls[a:b]])  # (chunks of `population`)
         got_cr = None if crash is None else np.concatenate([x[1] for x in rec.calls[a:b]])
         assert all((x[2] == c0.init).all() and x[3] == c0.inst_id for x in rec.calls[a:b])
-        arg = {abi.PSG_SHRINK_TAIL: cp, abi.PSG_SHRINK_LINK: 4 * P}.get(level, 0)
-        want_ho, want_cr = candidates(ho, crash, level, arg, n, R, adv.self_bit)
-        if mode == "liveness":  # the host drops candidates with too few live rounds before it evaluates
-            want_ho = want_ho[adv._live_count(want_ho) >= adv.live_rounds]
         assert want_ho.shape == got_ho.shape and (want_ho == got_ho).all(), (name, len(level_at), level)
         assert crash is None or (want_cr == got_cr).all()
         if level == abi.PSG_SHRINK_LINK:
